@@ -9,12 +9,17 @@ normalisation) + host Pade of the 30x30 Hessenberg + the beta*V*coef combine, wi
 One unit of the metric = one Krylov step ("matvec"), so an expv at m = 30 is 30 units.  Every rank runs its own
 independent (A, b) problem (weak scaling, no data-path collective); value = N * K * 30 / max-over-ranks wall time.
 
-The same JSON line carries, measured in the same process on rank 0 at N = 1:
+A plain run sets up, warms up, times the K steps and prints the result line, nothing else.  With --full the same JSON
+line also carries, measured in the same process on rank 0 at N = 1:
+  value_cold    the K steps measured first in the process, before the device spin-up
   roofline      dominant kernel (the single-pass Krylov step): SURVEY §8d bytes per launch / mean launch time
   secondary     the other ways into the same path -- split API (arnoldi! + expv!), outputs complete on return (the
                 C-ABI default), the Lanczos variant, config 4 (kiops, complex) and config 5 on one GPU
   cpu_baseline  the plain-C restatement of the reference loop on the host cores: all threads, one thread, and
                 scipy's expm_multiply (a different algorithm, labelled as such)
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (rank 0; float64, or
+float32 for a 32-bit path), so that two builds can be compared output for output: the inputs are seeded.
 """
 import argparse
 import json
@@ -38,6 +43,33 @@ C2_SYM_VALS = (0.5, 1.0, -3.0, 1.0, 0.5)       # symmetric      -> Lanczos path
 
 
 LINE_LIMIT = 4000     # the driver keeps the tail of stdout: the LAST line must fit (<= 4 KB)
+DUMP_LIMIT = 64 << 20  # --dump-outputs: bytes in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (torch tensors are copied to the host), float32 stays float32, every
+    other real type is written as float64.  The caller keeps the total within DUMP_LIMIT (a seeded sample of a larger output)."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+        if np.iscomplexobj(a):
+            raise TypeError("--dump-outputs: %s is complex" % name)
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_LIMIT))
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def sample_columns(W, seed=2024):
+    """A fixed, seeded sample of the columns of an n x ncols result that fits DUMP_LIMIT (all of them when they fit):
+    returns (W[:, cols], cols)."""
+    n, ncols = W.shape
+    keep = max(1, min(ncols, DUMP_LIMIT // 2 // (8 * n)))
+    cols = np.arange(ncols) if keep == ncols else np.sort(np.random.default_rng(seed).choice(ncols, size=keep, replace=False))
+    return W[:, cols.tolist()], cols
 
 
 def _r(x, sig=9):
@@ -386,6 +418,8 @@ def run_c3(args, eu, env, do_emit=True):
         u = step()
     env.barrier()
     elapsed_local = time.perf_counter() - t0
+    if getattr(args, "dump_outputs", "") and rank == 0:
+        dump_outputs(args.dump_outputs, {"u": u})
     apps = sh.applications - a0
     units, elapsed = D.aggregate_throughput(apps, elapsed_local, device=env.device)
     units /= world                                     # every rank counts the same (replicated) applications
@@ -452,6 +486,9 @@ def run_c5(args, eu, env, n=100_000, m=M_KRYLOV, do_emit=True, dtype=np.float64)
         W = step()
     env.barrier()
     elapsed_local = time.perf_counter() - t0
+    if getattr(args, "dump_outputs", "") and rank == 0:       # (the gathered n x nprob result: a seeded sample of its columns)
+        Ws, cols = sample_columns(W)
+        dump_outputs(args.dump_outputs, {"W": Ws, "W_columns": cols})
     units, elapsed = D.aggregate_throughput((hi - lo) * m * args.steps, elapsed_local, device=env.device)
     # ---- the final gather alone (untimed extra): the one collective of the path, n x nprob fp64 over all ranks ----
     gather_ms = None
@@ -1141,10 +1178,13 @@ def main(argv=None):
     ap.add_argument("--n", "--rows", dest="n", type=int, default=N_ROWS, help="override problem size (debug only; invalidates the metric)")
     ap.add_argument("--ortho", default="auto", choices=["auto", "mgs", "lowsync"])
     ap.add_argument("--spinup", type=float, default=0.6, help="seconds of untimed calls before the warm-up steps (device clocks; 0 = none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (split API, Lanczos, C4, C5)")
-    ap.add_argument("--no-c3-full", action="store_true", help="secondary block: skip BASELINE configs[2] at its largest single-GPU size (n = 163 840, 214.7 GB)")
-    ap.add_argument("--no-serial-pass", action="store_true", help="skip the extra non-overlapped profiling pass")
+    ap.add_argument("--full", action="store_true", help="c2: also the cold figure, the per-kernel roofline passes, the secondary "
+                                                        "measurements and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary measurements (split API, Lanczos, C4, C5)")
+    ap.add_argument("--no-c3-full", action="store_true", help="--full, secondary block: skip BASELINE configs[2] at its largest single-GPU size (n = 163 840, 214.7 GB)")
+    ap.add_argument("--no-serial-pass", action="store_true", help="--full: skip the extra non-overlapped profiling pass")
     ap.add_argument("--sync-outputs", action="store_true", help="every call returns only when its device result is complete")
     ap.add_argument("--split-api", action="store_true", help="time arnoldi!(Ks,A,b) + expv!(w,t,Ks) instead of expv(t,A,b)")
     ap.add_argument("--config", default="c2", choices=["c2", "c5", "c3"],
@@ -1160,6 +1200,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become the launcher (the driver's own form, torch.distributed.run, sets WORLD_SIZE)
         raise SystemExit(launch_ranks(args.gpus, argv))
@@ -1235,10 +1277,10 @@ def run_c2(args, eu, env):
 
     # device spin-up (untimed, before the W warm-up steps of the contract): a box that has just been handed over clocks up during
     # its first few hundred milliseconds of work -- the first run on a fresh box measured 3 % below the second (26.1 k vs 26.9 k)
-    # ... and the figure WITHOUT that spin-up, measured first in the process (VERDICT r5 / ADVICE r5): the contract's W warm-up steps,
-    # then the same K steps -- what the first calls of an ODE integrator see on a box that has been idle (`value_cold` in the line)
+    # ... and (--full) the figure WITHOUT that spin-up, measured first in the process (VERDICT r5 / ADVICE r5): the contract's W warm-up
+    # steps, then the same K steps -- what the first calls of an ODE integrator see on a box that has been idle (`value_cold` in the line)
     cold = None
-    if env.ctx is not None and args.spinup > 0:
+    if args.full and env.ctx is not None and args.spinup > 0:
         for _ in range(args.warmup):
             one_expv()
         env.barrier()
@@ -1264,6 +1306,8 @@ def run_c2(args, eu, env):
         units += one_expv()
     env.barrier()
     elapsed_local = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                        # (before any later pass overwrites w)
+        dump_outputs(args.dump_outputs, {"w": w})
     elapsed = max(env.per_rank(elapsed_local))                 # MAX over ranks
     units_total = float(sum(env.per_rank(units)))              # SUM over ranks
     value = units_total / elapsed
@@ -1276,9 +1320,9 @@ def run_c2(args, eu, env):
         if not (all(np.isfinite(chk)) and len(set(chk)) == world):
             raise SystemExit("config 2 at %d ranks: per-rank results are not %d distinct finite vectors: %s" % (world, world, chk))
 
-    # ---- per-kernel HIP-event timing of the same K steps (separate pass: events perturb the headline) ---
+    # ---- (--full) per-kernel HIP-event timing of the same K steps (separate pass: events perturb the headline) ---
     prof = {}
-    if ctx is not None:
+    if args.full and ctx is not None:
         ctx.prof_reset()
         ctx.prof_enable(True)
         for _ in range(args.steps):
@@ -1361,9 +1405,10 @@ def run_c2(args, eu, env):
                    "value_cold": cold["value"] if cold else None, "ms_per_step_cold": cold["ms_per_step"] if cold else None},
         "ranks_seen": seen, "devices": ids, "per_rank_ms_per_step": per_rank_ms, "process_group": env.backend,
         "counters": ctx.counters() if ctx is not None else None,
-        "roofline": roofline,
     }
-    if rank == 0 and world == 1 and not args.no_secondary and n == N_ROWS and not args.split_api and ctx is not None:
+    if args.full:
+        out["roofline"] = roofline
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and n == N_ROWS and not args.split_api and ctx is not None:
         sec = secondary_block(args, eu, env, op, b, w, n, nnz, m)
         # the driver's record keeps the head of this line: the figures the verdicts ask about are repeated up front, in
         # `config` (the full entries follow in `secondary`)
@@ -1384,7 +1429,7 @@ def run_c2(args, eu, env):
         out["config"]["reordered_setup_s"] = {k_: [round(float(sec[k_]["setup_s"]), 3), round(float(sec[k_]["setup_again_s"]), 3)]
                                     for k_ in ("general_sparse_rcm", "general_sparse_rcm_grid", "general_sparse_mesh") if k_ in sec and "setup_again_s" in sec[k_]}
         out["secondary"] = sec
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and ctx is not None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and ctx is not None:
         eu.expv(T_FINAL, op, b, m=m, ishermitian=False, ortho=args.ortho, out=w)
         env.sync()
         out["cpu_baseline"] = cpu_baseline_block(A, b_host, w.cpu().numpy(), m, n)

@@ -260,6 +260,49 @@ def test_bench_gpus_2_launches_two_ranks_by_itself(cfg):
         assert out["scaling"] == "weak" and out["value"] > 0
 
 
+@pytest.mark.parametrize("cfg,name", [(["--config", "c2", "--n", "300"], "w"), (["--config", "c5", "--n5", "96", "--nprob", "5"], "W"),
+                                      (["--config", "c3", "--n3", "101"], "u")])
+def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path, cfg, name):
+    """--dump-outputs DIR writes the result of the last timed step as DIR/<name>.npy in float64; a second run with the same arguments
+    writes the same array (seeded inputs).  A plain c2 run carries no roofline / cpu_baseline (those are --full)."""
+    got = []
+    for k in range(2):
+        d = str(tmp_path / str(k))
+        r, out, lines = _run_bench(["--gpus", "1", "--dump-outputs", d] + cfg)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert out["steps"] == 2 and "cpu_baseline" not in out
+        assert name != "w" or "roofline" not in out
+        got.append(np.load(os.path.join(d, name + ".npy")))
+    assert got[0].dtype == np.float64 and got[0].size > 0 and np.all(np.isfinite(got[0]))
+    assert np.array_equal(got[0], got[1])
+    if name == "w":
+        import sys
+        sys.path.insert(0, ROOT)
+        import bench
+        from oracle import krylov_oracle as ko
+        ref = ko.expv(1.0, bench.c2_operator(300), np.random.default_rng(3).standard_normal(300), m=30)
+        assert np.linalg.norm(got[0] - ref) <= 1e-14 * np.linalg.norm(ref)
+
+
+def test_bench_dump_samples_large_outputs_within_the_limit(tmp_path, monkeypatch):
+    """A result larger than the dump limit is written as a fixed, seeded sample of its columns (and their indices); a dump past the
+    limit is refused."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 8 * 100 * 20)
+    W = torch.arange(100 * 50, dtype=torch.float64).reshape(100, 50)
+    Ws, cols = bench.sample_columns(W)
+    Ws2, cols2 = bench.sample_columns(W)
+    assert len(cols) == 10 and np.array_equal(cols, cols2) and np.all(np.diff(cols) > 0)
+    assert torch.equal(Ws, W[:, cols.tolist()]) and torch.equal(Ws, Ws2)
+    bench.dump_outputs(str(tmp_path), {"W": Ws, "W_columns": cols})
+    assert np.array_equal(np.load(str(tmp_path / "W.npy")), W.numpy()[:, cols])
+    assert np.array_equal(bench.sample_columns(W[:, :5])[1], np.arange(5))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path), {"W": W})
+
+
 def test_bench_refuses_the_standin_outside_the_tests():
     """--standin swaps the product for an oracle-backed CPU solver inside the bench harness; a flag alone must not be
     enough to put its output into a bench line."""

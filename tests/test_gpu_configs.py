@@ -1357,17 +1357,17 @@ def test_float32_wave_form_on_general_diagonals(eu, shape):
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    """`python bench.py` (short): ONE JSON line with the keys the driver reads -- metric / value / unit / n_gpus / steps / warmup /
-    ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, a `roofline` object for the dominant
-    kernel (bound, achieved, peak, unit, frac, traffic) and a `cpu_baseline` object (value, unit, cores, kind, sample); value
-    consistent with ms_per_step, fraction below 1."""
+    """`python bench.py --full` (short): ONE JSON line with the keys the driver reads -- metric / value / unit / n_gpus / steps /
+    warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, a `roofline` object for the
+    dominant kernel (bound, achieved, peak, unit, frac, traffic) and a `cpu_baseline` object (value, unit, cores, kind, sample);
+    value consistent with ms_per_step, fraction below 1."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    # the command the driver runs (VERDICT r4 item 1), secondaries ON: the LAST stdout line is the record and must stay < 4 KB
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    # the driver's command (VERDICT r4 item 1) with --full, secondaries ON: the LAST stdout line is the record and must stay < 4 KB
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
                        cwd=root, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-2000:]
     out_lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -1401,6 +1401,34 @@ def test_bench_line_contract():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] in ("port", "reference") and c["value"] > 0 and c["cores"] >= 1
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_dumps_its_result(tmp_path):
+    """A plain `python bench.py --gpus 1 --steps K --warmup W` times the headline alone (no cold pass, roofline, secondary entries or
+    CPU baseline: those are --full) and prints one line with K timed steps; --dump-outputs DIR writes the w of the last timed step,
+    which is the expv of the seeded problem."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], cwd=root, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["dtype"] == "f64" and d["unit"] == "matvecs/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 30 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert "roofline" not in d and "cpu_baseline" not in d and "secondary_fracs" not in d["config"]
+    assert d["config"]["value_cold"] is None
+    w = np.load(os.path.join(str(tmp_path), "w.npy"))
+    assert w.dtype == np.float64 and w.shape == (1_000_000,)
+    n = w.size
+    wo, r = co.expv_csr(1.0, c2_operator(n), np.random.default_rng(3).standard_normal(n), m=30)
+    assert r["m"] == 30
+    close(w, wo, 1e-12, "bench.py --dump-outputs: w of the last timed step vs the C oracle (n = 1e6, m = 30)")
 
 
 def _bench_under_launcher(extra, timeout=900):

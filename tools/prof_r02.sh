@@ -3,7 +3,7 @@
 # kernel traces: default (overlapped) and serial mode; PMC: separate passes (FETCH_SIZE / WRITE_SIZE cannot share a pass,
 # SQ counters 8 per pass), all in serial mode so that a kernel's counters are its own.
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-CMD="python bench.py --no-cpu-baseline --no-secondary --no-serial-pass --steps 6 --warmup 2"
+CMD="python bench.py --full --no-cpu-baseline --no-secondary --no-serial-pass --steps 6 --warmup 2"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/p_default -o t -- $CMD > gpurun_out/p_default.log 2>&1
 EXPV_MI_PIPE_SERIAL=1 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/p_serial -o t -- $CMD > gpurun_out/p_serial.log 2>&1
 i=0

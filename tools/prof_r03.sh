@@ -5,7 +5,7 @@
 #  2. general-sparse / irregular / Float32 operators (tools/general_sparse.py): kernel stats + FETCH / WRITE passes
 #  3. dense GEMV (config 3, n = 32768): kernel stats + VALU-utilisation counters (why MFMA is not used)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-CMD="python bench.py --no-cpu-baseline --no-secondary --no-serial-pass --steps 6 --warmup 2"
+CMD="python bench.py --full --no-cpu-baseline --no-secondary --no-serial-pass --steps 6 --warmup 2"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/q_default -o t -- $CMD > gpurun_out/q_default.log 2>&1
 EXPV_MI_PIPE_SERIAL=1 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/q_serial -o t -- $CMD > gpurun_out/q_serial.log 2>&1
 i=0

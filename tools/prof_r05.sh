@@ -5,7 +5,7 @@
 #  3. FETCH_SIZE / WRITE_SIZE passes of the serial mode (separate runs) -> HBM traffic per launch of the step kernels (tools/pmc_summary.py)
 #  4. the same two counter passes + kernel stats for the ComplexF64 full-Arnoldi problem (tools/one_complex.py)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-CMD="python bench.py --no-cpu-baseline --no-secondary --no-serial-pass --steps 8 --warmup 2"
+CMD="python bench.py --full --no-cpu-baseline --no-secondary --no-serial-pass --steps 8 --warmup 2"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r5_default -o t -- $CMD > gpurun_out/r5_default.log 2>&1
 python tools/step_cadence.py gpurun_out/r5_default --skip 3 > gpurun_out/r05_step_cadence.txt 2>&1
 grep "^{" gpurun_out/r5_default.log | tail -1 > gpurun_out/r05_bench_under_rocprof_default.json
