@@ -347,16 +347,72 @@ def _empty_like(ref, shape, dtype):
 # ---------------------------------------------------------------------------------------------
 # operators (the contract of docs/src/interfaces.md:7-36)
 # ---------------------------------------------------------------------------------------------
-class MIOperator:
-    """Device-resident operator: scipy CSC/CSR matrix, dense ndarray, or a matrix-free callable.
+def _is_torch_sparse(A):
+    """a torch tensor of any layout but the strided one"""
+    if not _is_torch(A) or not hasattr(A, "layout"):
+        return False
+    import torch
+    return A.layout != torch.strided
 
-    ``MIOperator(A)`` uploads once (CSC is converted to CSR32 on the way; setup cost).  Exposes
-    ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian), ``nnz`` and ``opnorm_inf``.
+
+def _unpack_torch_sparse(A):
+    """The parts of a 2-D, square, non-batched ``torch.sparse_csr`` / ``torch.sparse_csc`` tensor, on whatever device it lives:
+    ``(fmt, ptr, idx, vals, shape)`` with fmt "csr" (ptr = crow_indices, idx = col_indices) or "csc" (ptr = ccol_indices,
+    idx = row_indices), the index tensors int32 or int64 and contiguous, the values float32 / float64 / complex64 / complex128.
+    No copy of anything that is contiguous already; nothing moves between devices."""
+    import torch
+    if A.layout == torch.sparse_csr:
+        fmt, ptr, idx = "csr", A.crow_indices(), A.col_indices()
+    elif A.layout == torch.sparse_csc:
+        fmt, ptr, idx = "csc", A.ccol_indices(), A.row_indices()
+    else:
+        raise TypeError(f"sparse torch tensors must have layout torch.sparse_csr or torch.sparse_csc, not {A.layout} "
+                        "(convert with .to_sparse_csr() / .to_sparse_csc())")
+    if A.dim() != 2 or ptr.dim() != 1:
+        raise DimensionMismatch("a sparse operator is one 2-D matrix (no batch dimensions)")
+    if A.shape[0] != A.shape[1]:
+        raise DimensionMismatch("operator must be square")
+    vals = A.values()
+    if vals.dim() != 1:
+        raise DimensionMismatch("a sparse operator has scalar entries (no dense dimensions)")
+    if vals.dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
+        raise TypeError(f"sparse operator values must be float32 / float64 / complex64 / complex128, not {vals.dtype}")
+    if ptr.dtype != idx.dtype or ptr.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"sparse operator indices must be int32 or int64, not {ptr.dtype} / {idx.dtype}")
+    return fmt, ptr.contiguous(), idx.contiguous(), vals.contiguous(), (int(A.shape[0]), int(A.shape[1]))
+
+
+def _torch_sparse_to_scipy(A):
+    """a CPU torch.sparse_csr / sparse_csc tensor as the scipy matrix of the same format (shares the arrays)"""
+    import scipy.sparse as sp
+    fmt, ptr, idx, vals, shape = _unpack_torch_sparse(A)
+    parts = (vals.numpy(), idx.numpy(), ptr.numpy())
+    return sp.csr_matrix(parts, shape=shape) if fmt == "csr" else sp.csc_matrix(parts, shape=shape)
+
+
+def _torch_ready(*tensors):
+    """the library works on its own stream: what torch has in flight for these tensors must be complete first (see _Arg)"""
+    import torch
+    st = torch.cuda.current_stream(tensors[0].device)
+    if not st.query():
+        st.synchronize()
+
+
+class MIOperator:
+    """Device-resident operator: scipy CSC/CSR matrix, ``torch.sparse_csr`` / ``torch.sparse_csc`` tensor, dense ndarray or
+    tensor, or a matrix-free callable.
+
+    ``MIOperator(A)`` uploads once (CSC is converted to CSR32 on the way; setup cost).  A sparse tensor that lives on the GPU is
+    taken where it is (expv_mi_op_create_csr_loc / _csc_loc): its index arrays are checked on the device, only the pattern visits
+    the host (``ingest_info``), the values never do.  Exposes ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian),
+    ``nnz`` and ``opnorm_inf``.
     """
 
     def __init__(self, A, ctx=None, dtype=None, ishermitian=None, matvec=None, shape=None, matvec_c=None):
         lib = L.load()
         self.ctx = ctx or default_context()
+        if _is_torch_sparse(A) and not A.is_cuda:      # a host matrix in torch's clothes: the scipy path
+            A = _torch_sparse_to_scipy(A)
         self.src = A
         h = C.c_void_p()
         self._cb = None
@@ -390,6 +446,19 @@ class MIOperator:
             self._cb = L.MATVEC_FN(_cb)
             _check(lib.expv_mi_op_create_callback(self.ctx._h, _code(dt), n, self._cb, None,
                                                   int(bool(ishermitian)), 0, C.byref(h)), self.ctx._h)
+        elif _is_torch_sparse(A):       # CSR / CSC arrays that live on the device: no host copy made here
+            fmt, ptr, idx, vals, shp = _unpack_torch_sparse(A)
+            if A.device.index not in (None, self.ctx.device):
+                raise ValueError(f"sparse tensor lives on {A.device}, the context on device {self.ctx.device}")
+            dt = _work_dtype(_np_dtype_of(vals) if dtype is None else dtype)
+            if vals.dtype != _torch_dtype(dt):
+                vals = vals.to(_torch_dtype(dt))      # (on the device)
+            _torch_ready(ptr, idx, vals)
+            self._sp_format, self._sp_sorted = fmt, True
+            self._dev_parts = (ptr, idx)              # pattern of the caller's arrays: update_values compares, astype rebuilds
+            create = lib.expv_mi_op_create_csr_loc if fmt == "csr" else lib.expv_mi_op_create_csc_loc
+            _check(create(self.ctx._h, _code(dt), shp[0], int(idx.numel()), ptr.data_ptr(), idx.data_ptr(), vals.data_ptr(),
+                          ptr.element_size(), 0, L.DEVICE, C.byref(h)), self.ctx._h)
         elif hasattr(A, "tocsc") and (hasattr(A, "indptr") or hasattr(A, "tocsr")):
             if not hasattr(A, "indptr"):
                 A = A.tocsr()
@@ -458,6 +527,8 @@ class MIOperator:
                 self.src_dtype = np.dtype(dtype or np.float64)
             elif hasattr(A, "indptr") or isinstance(A, np.ndarray):
                 self.src_dtype = np.dtype(A.dtype)
+            elif _is_torch_sparse(A):
+                self.src_dtype = _np_dtype_of(A.values())
             else:
                 self.src_dtype = _np_dtype_of(A)
         except Exception:
@@ -488,15 +559,32 @@ class MIOperator:
                 "mean_ring": (float(out[4]) / int(out[2])) if out[2] else 0.0, "tiles_ring_over_128": int(out[5]),
                 "column_indices_stored": int(out[6]), "ring_entries_per_tile": int(out[7])}
 
+    @property
+    def ingest_info(self):
+        """How a sparse operator came to be (expv_mi_op_ingest_info): ``from_device`` -- created from arrays on the device --,
+        the bytes of pattern and of values that were brought to the host for it (values: 0 unless a row is unsorted or holds a
+        duplicate), the creation time and the share of the device checks, and whether the ordering plan came from the plan cache."""
+        out = (C.c_int64 * 8)()
+        _check(L.load().expv_mi_op_ingest_info(self._h, out))
+        return {"from_device": bool(out[0]), "pattern_bytes_to_host": int(out[1]), "value_bytes_to_host": int(out[2]),
+                "create_s": 1e-6 * int(out[3]), "ingest_s": 1e-6 * int(out[4]), "plan_cached": bool(out[5])}
+
     def update_values(self, A):
         """New values on the same sparsity pattern (expv_mi_op_update_values): ``A`` is the matrix the operator was created
-        from after an in-place change of its values (same format, sorted indices), a device tensor or an array of nnz values
-        in that order.  The stored device forms are refilled and ishermitian / opnorm_inf re-evaluated, ~10x cheaper than a
-        new MIOperator."""
+        from after an in-place change of its values (same format, sorted indices; for an operator made from a sparse device
+        tensor: a tensor of the same layout, shape and nnz), a device tensor or an array of nnz values in that order.  The stored
+        device forms are refilled and ishermitian / opnorm_inf re-evaluated, ~10x cheaper than a new MIOperator."""
         fmt = getattr(self, "_sp_format", None)
         if fmt is None:
             raise ValueError("update_values: sparse operators only")
-        if hasattr(A, "indptr"):
+        if _is_torch_sparse(A):
+            if not hasattr(self, "_dev_parts"):
+                raise ValueError("update_values: a sparse tensor refreshes an operator that was created from one")
+            f2, ptr, idx, vals, shp = _unpack_torch_sparse(A)
+            if f2 != fmt or shp != self.shape or int(idx.numel()) != self.nnz or not A.is_cuda:
+                raise ValueError("update_values: same layout, shape and nnz as at creation required (on the device)")
+            self.src = A
+        elif hasattr(A, "indptr"):
             if A.format != fmt or not A.has_sorted_indices or A.nnz != self.nnz or A.shape != self.shape:
                 raise ValueError("update_values: same format, shape and (sorted) pattern as at creation required")
             vals = A.data
@@ -508,6 +596,13 @@ class MIOperator:
         _check(L.load().expv_mi_op_update_values(self._h, arg.ptr, arg.loc), self.ctx._h)
         if hasattr(A, "indptr"):
             self.src = A
+        elif hasattr(self, "_dev_parts") and not _is_torch_sparse(A):
+            # device-born operator refreshed with bare values: what astype rebuilds from is the creation pattern + these values
+            import torch
+            ptr, idx = self._dev_parts
+            v = arg.keep if arg.loc == L.DEVICE else torch.as_tensor(arg.host, device=ptr.device)
+            mk = torch.sparse_csr_tensor if fmt == "csr" else torch.sparse_csc_tensor
+            self.src = mk(ptr, idx, v.reshape(-1), size=self.shape)
         n_, nnz, herm, opn, dtc = C.c_int64(), C.c_int64(), C.c_int(), C.c_double(), C.c_int()
         _check(L.load().expv_mi_op_info(self._h, C.byref(n_), C.byref(nnz), C.byref(herm), C.byref(opn), C.byref(dtc)))
         self.ishermitian = bool(herm.value)
@@ -580,7 +675,10 @@ def _as_operator(A, want_dtype=None, ctx=None):
     """Resolve the operator argument of an API call.  An explicit MIOperator is the way to reuse an upload across calls.
     Host matrices (scipy sparse / ndarray) passed directly are uploaded on first use and the upload is reused ONLY while
     (same object, same context, same content fingerprint) -- an in-place ``A.data[:] = ...`` / ``A *= dt`` between calls
-    re-uploads, like the reference reading A at call time.  Device tensors are wrapped without a copy every time."""
+    re-uploads, like the reference reading A at call time.  Device tensors are wrapped without a copy every time; that goes for
+    sparse device tensors (``torch.sparse_csr`` / ``torch.sparse_csc``) too, whose operator is built anew at every call -- the
+    device checks, the pattern's trip to the host planners, the fill of the stored forms; the plan cache spares a repeated
+    pattern its ordering.  Reuse across calls is by an explicit ``MIOperator(A)`` (+ ``update_values``)."""
     if hasattr(A, "tocsr") and not hasattr(A, "indptr"):      # COO / DIA / LIL / ... : any scipy sparse matrix is an AbstractMatrix
         A = A.tocsr()
     if isinstance(A, MIOperator):

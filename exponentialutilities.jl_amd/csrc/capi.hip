@@ -8,6 +8,7 @@
 #include <type_traits>
 #include <cstring>
 #include <dlfcn.h>
+#include <functional>
 #include <unordered_map>
 
 #include "engine.h"
@@ -40,30 +41,35 @@ int guarded(Ctx *ctx, F &&f) {
   }
 }
 
-// CSC (any index base) -> CSR32, rows sorted by column; also the transpose for the Hermitian test
-template <class V>
-void csc_to_csr(int64_t n, const int64_t *colptr, const int64_t *rowval, const V *nz, int base, std::vector<int32_t> &rp,
-                std::vector<int32_t> &ci, std::vector<V> &va, std::vector<int32_t> *pos = nullptr) {
-  const int64_t nnz = colptr[n] - base;
+// CSC (any index base) -> CSR32, rows sorted by column.  The pattern alone: pos[k] is where entry k of the caller's arrays lives in CSR
+// order (the values follow through it: here on the host, or on the device by dev::op_scatter_values)
+template <class I>
+void csc_to_csr_pattern(int64_t n, const I *colptr, const I *rowval, int base, std::vector<int32_t> &rp, std::vector<int32_t> &ci,
+                        std::vector<int32_t> &pos) {
+  const int64_t nnz = (int64_t)colptr[n] - base;
   rp.assign(n + 1, 0);
   ci.resize(nnz);
-  va.resize(nnz);
   for (int64_t k = 0; k < nnz; ++k) {
-    const int64_t r = rowval[k] - base;
+    const int64_t r = (int64_t)rowval[k] - base;
     if (r < 0 || r >= n) fail(EXPV_MI_ARGUMENT_ERROR, "sparse operator: row index out of range");
     rp[r + 1]++;
   }
   for (int64_t r = 0; r < n; ++r) rp[r + 1] += rp[r];
   std::vector<int32_t> fill(rp.begin(), rp.end() - 1);
-  if (pos) pos->resize(nnz);
+  pos.resize(nnz);
   for (int64_t c = 0; c < n; ++c)
-    for (int64_t k = colptr[c] - base; k < colptr[c + 1] - base; ++k) {
-      const int64_t r = rowval[k] - base;
-      const int32_t dst = fill[r]++;
+    for (int64_t k = (int64_t)colptr[c] - base; k < (int64_t)colptr[c + 1] - base; ++k) {
+      const int32_t dst = fill[(int64_t)rowval[k] - base]++;
       ci[dst] = (int32_t)c;
-      va[dst] = nz[k];
-      if (pos) (*pos)[k] = dst;      // where entry k of the caller's arrays lives in CSR order (values-only updates)
+      pos[k] = dst;
     }
+}
+template <class V>
+void csc_to_csr(int64_t n, const int64_t *colptr, const int64_t *rowval, const V *nz, int base, std::vector<int32_t> &rp,
+                std::vector<int32_t> &ci, std::vector<V> &va, std::vector<int32_t> &pos) {
+  csc_to_csr_pattern<int64_t>(n, colptr, rowval, base, rp, ci, pos);
+  va.resize(pos.size());
+  for (size_t k = 0; k < pos.size(); ++k) va[(size_t)pos[k]] = nz[k];
 }
 
 using dense::cf;
@@ -172,16 +178,18 @@ void csr_props(int64_t n, const std::vector<int32_t> &rp, const std::vector<int3
   *herm = h ? 1 : 0;
 }
 
+// the CSR32 arrays of an operator: the pattern, and the values when the creator holds them on the host (va == nullptr: the value
+// array is allocated only -- a creator with device values fills it there)
 template <class V>
-void upload_csr(Op &op, const std::vector<int32_t> &rp, const std::vector<int32_t> &ci, const std::vector<V> &va) {
+void upload_csr(Op &op, const std::vector<int32_t> &rp, const std::vector<int32_t> &ci, const std::vector<V> *va) {
   Ctx *c = op.ctx;
   op.rowptr.alloc(sizeof(int32_t) * rp.size());
   op.col.alloc(sizeof(int32_t) * std::max<size_t>(ci.size(), 1));
-  op.val.alloc(sizeof(V) * std::max<size_t>(va.size(), 1));
+  op.val.alloc(sizeof(V) * std::max<size_t>(ci.size(), 1));
   HIPCHECK(hipMemcpyAsync(op.rowptr.p, rp.data(), sizeof(int32_t) * rp.size(), hipMemcpyHostToDevice, c->stream));
   if (!ci.empty()) {
     HIPCHECK(hipMemcpyAsync(op.col.p, ci.data(), sizeof(int32_t) * ci.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(hipMemcpyAsync(op.val.p, va.data(), sizeof(V) * va.size(), hipMemcpyHostToDevice, c->stream));
+    if (va) HIPCHECK(hipMemcpyAsync(op.val.p, va->data(), sizeof(V) * va->size(), hipMemcpyHostToDevice, c->stream));
   }
   HIPCHECK(hipStreamSynchronize(c->stream));
 }
@@ -712,19 +720,23 @@ static OrderPlanCache &plan_cache() { static OrderPlanCache c; return c; }
 // the plan being recorded by the creation in progress on this thread (install_row_order / upload_patch_plan write into it)
 static thread_local OrderPlan *g_plan_rec = nullptr;
 
-template <class V>
+// What a planner does with the creator's values when it installs a row order.  The planners work on the PATTERN alone; a creator
+// that holds the values on the host hands them a function that carries its copy along (va2[k] = va[src[k]]), a creator whose values
+// stay on the device hands them none -- those values go to their stored places through op.csc_pos afterwards (place_values_device).
+using ValuePermuter = std::function<void(const std::vector<int32_t> &src)>;
 static void install_row_order(Op &op, int64_t n, const std::vector<int32_t> &perm, const std::vector<int32_t> &src, std::vector<int32_t> &rp,
-                              std::vector<int32_t> &ci, std::vector<V> &va, std::vector<int32_t> &rp2, std::vector<int32_t> &ci2, int64_t bw0, int64_t bw1,
+                              std::vector<int32_t> &ci, const ValuePermuter &pv, std::vector<int32_t> &rp2, std::vector<int32_t> &ci2, int64_t bw0, int64_t bw1,
                               std::chrono::steady_clock::time_point t0);
 // widest band (rows) an operator takes the patch form in its own ordering with: an eighth of a tile (ring <= a quarter of the tile's rows)
 static inline int64_t banded_ring_max(int value_bytes) { return (int64_t)(16 / value_bytes) * dev::BLOCK / 8; }
 template <class V>
-static bool try_patch_order(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, std::vector<V> &va, bool mesh, int64_t bw0,
+static bool try_patch_order(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, const ValuePermuter &pv, bool mesh, int64_t bw0,
                             const reorder::Graph *G = nullptr);
 // Reverse Cuthill-McKee at creation (context option "reorder"; reorder.h): kept when it moves the operator to a better step form.
-// On return rp / ci / va hold P A P' and op.perm the ordering; op.csc_pos maps the caller's entries to the reordered CSR arrays.
+// On return rp / ci hold the pattern of P A P' (the creator's host values, if any, went along through `pv`) and op.perm the ordering;
+// op.csc_pos maps the caller's entries to the reordered CSR arrays.
 template <class V>
-static void maybe_reorder(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, std::vector<V> &va, PatternCache &pc) {
+static void maybe_reorder(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, const ValuePermuter &pv, PatternCache &pc) {
   const int mode = op.ctx->opt.reorder;
   if (mode == 0 || n < 2 || ci.empty()) return;
   const auto t0 = std::chrono::steady_clock::now();
@@ -755,7 +767,7 @@ static void maybe_reorder(Op &op, int64_t n, std::vector<int32_t> &rp, std::vect
   lap("pattern class");
   const reorder::Graph G(n, rp.data(), ci.data());      // the adjacency of A + A': built once, shared by every attempt below
   lap("adjacency of A + A'");
-  auto mesh = [&]() { return mode == 1 && !P0.overflow && try_patch_order<V>(op, n, rp, ci, va, true, P0.bandwidth, &G); };
+  auto mesh = [&]() { return mode == 1 && !P0.overflow && try_patch_order<V>(op, n, rp, ci, pv, true, P0.bandwidth, &G); };
   std::vector<int32_t> perm;
   bool mesh_tried = false;
   if (mode == 1 && op.ctx->opt.patch && !P0.overflow) {
@@ -779,7 +791,7 @@ static void maybe_reorder(Op &op, int64_t n, std::vector<int32_t> &rp, std::vect
   if (c1.cls < 3 && !mesh_tried && mesh()) return;
   const bool better = c1.cls > c0.cls || (c1.cls == c0.cls && c1.cls == 2 && 4 * c1.reach <= c0.reach);
   if (mode == 1 && !better) return;
-  install_row_order<V>(op, n, perm, src, rp, ci, va, rp2, ci2, P0.bandwidth, P1.bandwidth, t0);
+  install_row_order(op, n, perm, src, rp, ci, pv, rp2, ci2, P0.bandwidth, P1.bandwidth, t0);
   lap("values + maps + uploads");
 }
 
@@ -864,12 +876,10 @@ static std::vector<int32_t> patch_order(int64_t n, int64_t k, int64_t R, int64_t
   return perm;
 }
 
-template <class V>
 static void install_row_order(Op &op, int64_t n, const std::vector<int32_t> &perm, const std::vector<int32_t> &src, std::vector<int32_t> &rp,
-                              std::vector<int32_t> &ci, std::vector<V> &va, std::vector<int32_t> &rp2, std::vector<int32_t> &ci2, int64_t bw0, int64_t bw1,
+                              std::vector<int32_t> &ci, const ValuePermuter &pv, std::vector<int32_t> &rp2, std::vector<int32_t> &ci2, int64_t bw0, int64_t bw1,
                               std::chrono::steady_clock::time_point t0) {
-  std::vector<V> va2(va.size());
-  for (size_t k = 0; k < va2.size(); ++k) va2[k] = va[(size_t)src[k]];
+  if (pv) pv(src);
   // caller's entry j -> its place in the reordered arrays (values-only updates scatter through this map)
   std::vector<int32_t> place(src.size());
   for (size_t k = 0; k < src.size(); ++k) place[(size_t)src[k]] = (int32_t)k;
@@ -899,7 +909,6 @@ static void install_row_order(Op &op, int64_t n, const std::vector<int32_t> &per
   }
   rp.swap(rp2);
   ci.swap(ci2);
-  va.swap(va2);
   op.perm = pm;
 }
 
@@ -1030,10 +1039,10 @@ static bool plan_patch_from_perm(int64_t n, const int32_t *rp, const int32_t *ci
 }
 
 static void upload_patch_plan(Op &op, PatchPlan &pl);
-// returns true when the operator was put into the patch ordering (rp / ci / va then hold P A P', op.perm the ordering, op.ring_* the
+// returns true when the operator was put into the patch ordering (rp / ci then hold the pattern of P A P', op.perm the ordering, op.ring_* the
 // per-tile rings and the tile-local column array)
 template <class V>
-static bool try_patch_order(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, std::vector<V> &va, bool mesh, int64_t bw0,
+static bool try_patch_order(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, const ValuePermuter &pv, bool mesh, int64_t bw0,
                             const reorder::Graph *G) {
   if (!op.ctx->opt.patch || op.perm || n < 2 || ci.empty()) return false;
   // (every element type: V is double, float or their std::complex)
@@ -1042,7 +1051,7 @@ static bool try_patch_order(Op &op, int64_t n, std::vector<int32_t> &rp, std::ve
   if (mesh ? !plan_mesh_patch(n, rp.data(), ci.data(), (int64_t)ci.size(), (int)sizeof(V), bw0, pl, G)
            : !plan_patch(n, rp.data(), ci.data(), (int64_t)ci.size(), (int)sizeof(V), pl)) return false;
   upload_patch_plan(op, pl);
-  install_row_order<V>(op, n, pl.perm, pl.src, rp, ci, va, pl.rp2, pl.ci2, pl.bw0, pl.bw1, t0);
+  install_row_order(op, n, pl.perm, pl.src, rp, ci, pv, pl.rp2, pl.ci2, pl.bw0, pl.bw1, t0);
   return true;
 }
 // Banded operators wider than the halo form's 8 rows (up to 64) ran the wave form; the patch form in their own ordering replaces it.
@@ -1099,22 +1108,28 @@ static void upload_patch_plan(Op &op, PatchPlan &pl) {
   op.ring_over128 = pl.over128;
 }
 
-template <class V>
-void make_csr_op(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, std::vector<V> &va) {
-  static const bool tm = std::getenv("EXPV_MI_OP_TIMING") != nullptr;      // developer diagnostic: phases of an operator build
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what) {
-    if (!tm) return;
+// developer diagnostic: phases of an operator build (EXPV_MI_OP_TIMING)
+struct BuildLaps {
+  const bool on = std::getenv("EXPV_MI_OP_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+  void operator()(const char *what) {
+    if (!on) return;
     const auto t = std::chrono::steady_clock::now();
     std::fprintf(stderr, "[op build] %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
     t_last = t;
-  };
-  op.kind = OP_CSR;
-  op.n = n;
-  op.nnz = (int64_t)ci.size();
-  csr_props<V>(n, rp, ci, va, &op.ishermitian, &op.opnorm_inf);      // (both invariant under a symmetric permutation)
-  lap("ishermitian + opnorm");
-  PatternCache pc;
+  }
+};
+
+// Operator creation in four parts, so that a creator whose values never visit the host (create_sparse_device) runs the same
+// planners and layouts as one that holds them there (make_csr_op):
+//   plan_csr_pattern    the ordering plan of the PATTERN -- plan cache, reverse Cuthill-McKee, grid / mesh patches, the ring of a
+//                       banded operator; rp / ci come back as the pattern that is stored
+//   upload_csr          the CSR32 arrays (pattern; values when the creator has them on the host)
+//   build_csr_layouts   SELL / DIA / general-DIA layouts of the stored pattern (filled on the device: op_fill_forms)
+//   upload_tile_ranges  tile lo / hi of the wave form on SELL slots
+template <class V>
+static void plan_csr_pattern(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, const ValuePermuter &pv, PatternCache &pc,
+                             BuildLaps &lap) {
   // the ordering plan of this pattern: from the cache, or worked out now and kept
   OrderPlanCache &cache = plan_cache();
   std::shared_ptr<OrderPlan> plan;
@@ -1129,7 +1144,7 @@ void make_csr_op(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_
     const auto t0 = std::chrono::steady_clock::now();
     if (plan->reordered) {
       std::vector<int32_t> rp2 = plan->rp2, ci2 = plan->ci2;
-      install_row_order<V>(op, n, plan->perm, plan->src, rp, ci, va, rp2, ci2, plan->bw0, plan->bw1, t0);
+      install_row_order(op, n, plan->perm, plan->src, rp, ci, pv, rp2, ci2, plan->bw0, plan->bw1, t0);
     }
     if (plan->has_patch) {
       PatchPlan pl = *plan->patch;      // (upload pads its arrays)
@@ -1147,9 +1162,9 @@ void make_csr_op(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_
       g_plan_rec = rec.get();
     }
     struct RecOff { ~RecOff() { g_plan_rec = nullptr; } } rec_off;
-    maybe_reorder<V>(op, n, rp, ci, va, pc);
+    maybe_reorder<V>(op, n, rp, ci, pv, pc);
     lap("reordering (RCM)");
-    if (detect_grid2d_quick(pc.get(n, rp, ci, (int)sizeof(V)), n)) (void)try_patch_order<V>(op, n, rp, ci, va, false, 0);
+    if (detect_grid2d_quick(pc.get(n, rp, ci, (int)sizeof(V)), n)) (void)try_patch_order<V>(op, n, rp, ci, pv, false, 0);
     lap("grid-patch ordering");
     (void)try_banded_ring<V>(op, n, rp, ci, pc.get(n, rp, ci, (int)sizeof(V)));
     lap("tile-local columns of a banded operator");
@@ -1157,11 +1172,12 @@ void make_csr_op(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_
     // worth keeping: an ordering or a patch plan (a pattern that needed neither costs nothing to analyse again)
     if (rec && (rec->reordered || rec->has_patch)) cache.put(rec);
   }
-  upload_csr<V>(op, rp, ci, va);
-  lap("CSR upload");
+}
+
+template <class V>
+static void build_csr_layouts(Op &op, int64_t n, const std::vector<int32_t> &rp, const std::vector<int32_t> &ci, const PatternPlan &P, BuildLaps &lap) {
   build_sell<V>(op, n, rp, (int64_t)ci.size(), ci.data());
   lap("SELL layout");
-  const PatternPlan P = pc.get(n, rp, ci, (int)sizeof(V));
   op.rows_sorted_unique = P.sorted_unique;
   op.bandwidth = P.bandwidth;      // max |col - row|
   lap("pattern analysis");
@@ -1169,30 +1185,109 @@ void make_csr_op(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_
   lap("DIA layout");
   if (op.sell_ok && op.sell_cut == 0) build_gdia<V>(op, n, P);
   lap("general DIA");
+}
+
+template <class V>
+static void upload_tile_ranges(Op &op, int64_t n, const std::vector<int32_t> &rp, const std::vector<int32_t> &ci, const PatternPlan &P) {
+  if (!(op.sell_ok && P.tile_reach >= 0)) return;
+  // wave form on SELL slots: which tiles does a tile's piece of A read u from?
+  const int64_t TR = (16 / (int64_t)sizeof(V)) * 256, nt = (n + TR - 1) / TR;      // (the tile of the element type: analyze_pattern)
+  std::vector<int32_t> lo(nt), hi(nt);
+  for (int64_t t = 0; t < nt; ++t) {
+    int64_t cmin = INT64_MAX, cmax = -1;
+    for (int64_t r = t * TR; r < std::min<int64_t>(n, (t + 1) * TR); ++r)
+      for (int32_t k = rp[r]; k < rp[r + 1]; ++k) { cmin = std::min<int64_t>(cmin, ci[k]); cmax = std::max<int64_t>(cmax, ci[k]); }
+    if (cmax < 0) { cmin = t * TR; cmax = t * TR; }     // only empty rows: nothing but itself (padding slots read the own row)
+    lo[t] = (int32_t)(cmin / TR);
+    hi[t] = (int32_t)(cmax / TR);
+  }
+  op.tile_lo.alloc(sizeof(int32_t) * nt);
+  op.tile_hi.alloc(sizeof(int32_t) * nt);
+  HIPCHECK(hipMemcpyAsync(op.tile_lo.p, lo.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, op.ctx->stream));
+  HIPCHECK(hipMemcpyAsync(op.tile_hi.p, hi.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, op.ctx->stream));
+  HIPCHECK(hipStreamSynchronize(op.ctx->stream));
+  op.tile_reach = P.tile_reach;
+}
+
+// creation from arrays the caller holds on the host: the values travel with the pattern
+template <class V>
+void make_csr_op(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, std::vector<V> &va) {
+  BuildLaps lap;
+  op.kind = OP_CSR;
+  op.n = n;
+  op.nnz = (int64_t)ci.size();
+  csr_props<V>(n, rp, ci, va, &op.ishermitian, &op.opnorm_inf);      // (both invariant under a symmetric permutation)
+  lap("ishermitian + opnorm");
+  PatternCache pc;
+  const ValuePermuter carry = [&va](const std::vector<int32_t> &src) {
+    std::vector<V> va2(va.size());
+    for (size_t k = 0; k < va2.size(); ++k) va2[k] = va[(size_t)src[k]];
+    va.swap(va2);
+  };
+  plan_csr_pattern<V>(op, n, rp, ci, carry, pc, lap);
+  upload_csr<V>(op, rp, ci, &va);
+  lap("CSR upload");
+  const PatternPlan P = pc.get(n, rp, ci, (int)sizeof(V));
+  build_csr_layouts<V>(op, n, rp, ci, P, lap);
   {
     unsigned long long out[32];
     op_fill_forms<typename DevOf<V>::type>(op, true, false, out);
   }
   lap("device fill of the forms");
-  if (op.sell_ok && P.tile_reach >= 0) {
-    // wave form on SELL slots: which tiles does a tile's piece of A read u from?
-    const int64_t TR = (16 / (int64_t)sizeof(V)) * 256, nt = (n + TR - 1) / TR;      // (the tile of the element type: analyze_pattern)
-    std::vector<int32_t> lo(nt), hi(nt);
-    for (int64_t t = 0; t < nt; ++t) {
-      int64_t cmin = INT64_MAX, cmax = -1;
-      for (int64_t r = t * TR; r < std::min<int64_t>(n, (t + 1) * TR); ++r)
-        for (int32_t k = rp[r]; k < rp[r + 1]; ++k) { cmin = std::min<int64_t>(cmin, ci[k]); cmax = std::max<int64_t>(cmax, ci[k]); }
-      if (cmax < 0) { cmin = t * TR; cmax = t * TR; }     // only empty rows: nothing but itself (padding slots read the own row)
-      lo[t] = (int32_t)(cmin / TR);
-      hi[t] = (int32_t)(cmax / TR);
-    }
-    op.tile_lo.alloc(sizeof(int32_t) * nt);
-    op.tile_hi.alloc(sizeof(int32_t) * nt);
-    HIPCHECK(hipMemcpyAsync(op.tile_lo.p, lo.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, op.ctx->stream));
-    HIPCHECK(hipMemcpyAsync(op.tile_hi.p, hi.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, op.ctx->stream));
-    HIPCHECK(hipStreamSynchronize(op.ctx->stream));
-    op.tile_reach = P.tile_reach;
+  upload_tile_ranges<V>(op, n, rp, ci, P);
+}
+
+// Creation from arrays the caller holds on the DEVICE (expv_mi_op_create_csr_loc / _csc_loc): rp / ci are the normalised pattern
+// the ingest kernels checked (CSR32; for a CSC caller already turned into rows, op.csc_pos holding the map), `rp_dev` / `ci_dev` the
+// device copies of exactly these arrays when there are any (CSR callers), `vals` the caller's device values in the caller's entry
+// order.  The planners see the pattern only; the values go from the caller's buffer to their stored places on the device, and the
+// value-dependent properties come from the device evaluation that expv_mi_op_update_values uses.  Values reach the host in one
+// case only -- rows that are not sorted and free of duplicates, whose Hermitian test is the host's (as in op_update_values_T).
+template <class V>
+void make_csr_op_device(Op &op, int64_t n, std::vector<int32_t> &rp, std::vector<int32_t> &ci, DevBuf &rp_dev, DevBuf &ci_dev, const void *vals) {
+  using T = typename DevOf<V>::type;
+  BuildLaps lap;
+  hipStream_t s = op.ctx->stream;
+  op.kind = OP_CSR;
+  op.n = n;
+  op.nnz = (int64_t)ci.size();
+  PatternCache pc;
+  plan_csr_pattern<V>(op, n, rp, ci, nullptr, pc, lap);
+  if (!op.perm && rp_dev.p && ci_dev.p) {      // stored as the caller ordered it: the checked device copies ARE the CSR arrays
+    op.rowptr = std::move(rp_dev);
+    op.col = std::move(ci_dev);
+    op.val.alloc(sizeof(V) * std::max<size_t>(ci.size(), 1));
+  } else {
+    upload_csr<V>(op, rp, ci, nullptr);
   }
+  if (!ci.empty()) {
+    if (!op.csc_pos.empty()) {      // caller's entry j -> its stored place (a CSC caller, a reordered operator, or both)
+      op.csc_pos_dev.alloc(sizeof(int32_t) * op.csc_pos.size());
+      HIPCHECK(hipMemcpyAsync(op.csc_pos_dev.p, op.csc_pos.data(), sizeof(int32_t) * op.csc_pos.size(), hipMemcpyHostToDevice, s));
+      dev::op_scatter_values<T>(s, op.val.as<T>(), reinterpret_cast<const T *>(vals), op.csc_pos_dev.as<int32_t>(), op.nnz);
+    } else {
+      HIPCHECK(hipMemcpyAsync(op.val.p, vals, sizeof(V) * ci.size(), hipMemcpyDeviceToDevice, s));
+    }
+  }
+  lap("CSR arrays + values in place");
+  const PatternPlan P = pc.get(n, rp, ci, (int)sizeof(V));
+  build_csr_layouts<V>(op, n, rp, ci, P, lap);
+  unsigned long long out[32];
+  op_fill_forms<T>(op, true, op.rows_sorted_unique, out);
+  lap("device fill of the forms");
+  double opn;
+  std::memcpy(&opn, &out[0], sizeof(double));
+  op.opnorm_inf = opn;
+  if (op.rows_sorted_unique) {
+    op.ishermitian = out[1] ? 0 : 1;
+  } else {      // rows out of order: the host test on a downloaded copy of the values
+    std::vector<V> va(ci.size());
+    if (!va.empty()) HIPCHECK(hipMemcpy(va.data(), op.val.p, sizeof(V) * va.size(), hipMemcpyDeviceToHost));
+    double dummy;
+    csr_props<V>(n, rp, ci, va, &op.ishermitian, &dummy);
+    op.ingest[2] = (int64_t)(sizeof(V) * va.size());
+  }
+  upload_tile_ranges<V>(op, n, rp, ci, P);
 }
 
 // the device path computes in fp64 / complex-fp64 (include/expv_mi.h: expv_mi_dtype)
@@ -1497,7 +1592,7 @@ int expv_mi_op_create_csc(expv_mi_ctx_t ctx, int dtype, int64_t n, const int64_t
     dispatch_host_dtype(dtype, [&](auto tag) {
       using V = typename decltype(tag)::type;
       std::vector<V> va;
-      csc_to_csr<V>(n, colptr, rowval, reinterpret_cast<const V *>(nzval), index_base, rp, ci, va, &op->csc_pos);
+      csc_to_csr<V>(n, colptr, rowval, reinterpret_cast<const V *>(nzval), index_base, rp, ci, va, op->csc_pos);
       make_csr_op<V>(*op, n, rp, ci, va);
     });
     ctx->adopt(&op->ctx);
@@ -1546,6 +1641,126 @@ int expv_mi_op_create_csr(expv_mi_ctx_t ctx, int dtype, int64_t n, const void *r
     ctx->adopt(&op->ctx);
     *out = op.release();
   });
+}
+
+// ---- sparse operators from arrays that live on the device ------------------------------------------------------------------------
+namespace {
+// One body for CSR and CSC callers.  The caller's index arrays are checked and normalised by the ingest kernels (op_ingest.hip)
+// before anything -- on the device or here -- indexes by them; a violated condition is reported in the host creators' words and
+// nothing else has run.  Then only the normalised PATTERN comes to the host (4 (n + 1 + nnz) bytes: the planners live here).
+void create_sparse_device(Ctx *ctx, bool csc, int dtype, int64_t n, int64_t nnz, const void *ptr, const void *idx, const void *vals,
+                          int idx_bytes, int index_base, expv_mi_op_t *out) {
+  const std::string who = csc ? "op_create_csc" : "op_create_csr";
+  const char *pname = csc ? "colptr" : "rowptr";
+  const auto t_begin = std::chrono::steady_clock::now();
+  if (!out) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null output");
+  if (idx_bytes != 4 && idx_bytes != 8) fail(EXPV_MI_ARGUMENT_ERROR, who + ": idx_bytes must be 4 or 8");
+  if (n < 0 || n > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, who + ": n out of range for CSR32");
+  if (!ptr) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null " + pname);
+  check_device_dtype(dtype, who.c_str());
+  if (nnz < 0) fail(EXPV_MI_ARGUMENT_ERROR, who + ": negative nnz");
+  if (nnz > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, who + ": nnz exceeds CSR32");
+  if (nnz > 0 && (!idx || !vals)) fail(EXPV_MI_ARGUMENT_ERROR, who + (csc ? ": null colptr / rowval / nzval" : ": null colind / vals"));
+  hipStream_t s = ctx->stream;
+  DevBuf ptr32(sizeof(int32_t) * (size_t)(n + 1)), idx32(sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1) + 16), st_dev(sizeof(dev::IngestStatus));
+  dev::ingest_indices(s, idx_bytes, ptr, idx, n, nnz, index_base, ptr32.as<int32_t>(), idx32.as<int32_t>(), st_dev.as<dev::IngestStatus>());
+  dev::IngestStatus st;
+  HIPCHECK(hipMemcpyAsync(&st, st_dev.p, sizeof(st), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  const auto t_ingest = std::chrono::steady_clock::now();
+  auto at = [](unsigned long long pos) { return " (first at position " + std::to_string(pos) + ")"; };
+  if (st.flags & dev::INGEST_BAD_FIRST) fail(EXPV_MI_ARGUMENT_ERROR, who + ": " + pname + "[0] must equal the index base");
+  if (st.flags & dev::INGEST_DECREASING) fail(EXPV_MI_ARGUMENT_ERROR, who + ": " + pname + " must be non-decreasing" + at(st.first_ptr));
+  if (st.flags & dev::INGEST_BAD_NNZ) fail(EXPV_MI_ARGUMENT_ERROR, who + ": nnz must equal " + pname + "[n] - index base");
+  if (st.flags & dev::INGEST_BAD_INDEX)
+    fail(EXPV_MI_ARGUMENT_ERROR, (csc ? std::string("sparse operator: row index out of range") : who + ": column index out of range") + at(st.first_idx));
+  std::unique_ptr<expv_mi_op_s> op(new expv_mi_op_s());
+  op->ctx = ctx;
+  op->device = ctx->device;
+  op->dtype = dtype;
+  std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
+  HIPCHECK(hipMemcpyAsync(rp.data(), ptr32.p, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, s));
+  if (nnz > 0) HIPCHECK(hipMemcpyAsync(ci.data(), idx32.p, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  op->ingest[0] = 1;
+  op->ingest[1] = (int64_t)(sizeof(int32_t) * (rp.size() + ci.size()));
+  // every row strictly ascending, as counted on the device: what the host analysis of the stored pattern must find too for an
+  // operator that keeps a CSR caller's order (checked below; a CSC caller's rows are made here, sorted by construction)
+  const bool caller_sorted = st.desc_all == st.desc_starts;
+  if (csc) {      // columns -> rows, on the pattern; the device copies are of the caller's columns: not what is stored
+    std::vector<int32_t> rp2, ci2;
+    csc_to_csr_pattern<int32_t>(n, rp.data(), ci.data(), 0, rp2, ci2, op->csc_pos);
+    rp.swap(rp2);
+    ci.swap(ci2);
+    ptr32.release();
+    idx32.release();
+  }
+  dispatch_host_dtype(dtype, [&](auto tag) {
+    using V = typename decltype(tag)::type;
+    make_csr_op_device<V>(*op, n, rp, ci, ptr32, idx32, vals);
+  });
+  if (!csc && !op->perm && op->rows_sorted_unique != caller_sorted)
+    fail(EXPV_MI_ASSERTION, who + ": device and host disagree on whether the rows are sorted and free of duplicates");
+  const auto t_end = std::chrono::steady_clock::now();
+  op->ingest[3] = (int64_t)std::chrono::duration<double, std::micro>(t_end - t_begin).count();
+  op->ingest[4] = (int64_t)std::chrono::duration<double, std::micro>(t_ingest - t_begin).count();
+  op->ingest[5] = op->plan_cached ? 1 : 0;
+  ctx->adopt(&op->ctx);
+  *out = op.release();
+}
+}  // namespace
+
+int expv_mi_op_create_csr_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnz, const void *rowptr, const void *colind, const void *vals,
+                              int idx_bytes, int index_base, int loc, expv_mi_op_t *out) {
+  if (loc == EXPV_MI_HOST) {      // the host creator, which takes nnz from rowptr[n]: a stated nnz that differs is the caller's mistake
+    const int rc = guarded(ctx, [&] {
+      if ((idx_bytes == 4 || idx_bytes == 8) && rowptr && n >= 0 && n <= 0x7fffffffLL) {
+        const int64_t last = idx_bytes == 8 ? reinterpret_cast<const int64_t *>(rowptr)[n] : reinterpret_cast<const int32_t *>(rowptr)[n];
+        if (last - index_base != nnz) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_csr: nnz must equal rowptr[n] - index base");
+      }
+    });
+    return rc != EXPV_MI_OK ? rc : expv_mi_op_create_csr(ctx, dtype, n, rowptr, colind, vals, idx_bytes, index_base, out);
+  }
+  return guarded(ctx, [&] {
+    if (loc != EXPV_MI_DEVICE) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_csr: bad location");
+    ctx->use();
+    create_sparse_device(ctx, false, dtype, n, nnz, rowptr, colind, vals, idx_bytes, index_base, out);
+  });
+}
+
+int expv_mi_op_create_csc_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnz, const void *colptr, const void *rowval, const void *nzval,
+                              int idx_bytes, int index_base, int loc, expv_mi_op_t *out) {
+  if (loc == EXPV_MI_HOST) {      // the host creator reads 8-byte indices: 4-byte ones are widened for it
+    std::vector<int64_t> cp, rv;
+    const int rc = guarded(ctx, [&] {
+      if (idx_bytes != 4 && idx_bytes != 8) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_csc: idx_bytes must be 4 or 8");
+      if (n < 0 || n > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_csc: n out of range for CSR32");
+      if (nnz < 0 || nnz > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_csc: nnz exceeds CSR32");
+      if (!colptr || (nnz > 0 && (!rowval || !nzval))) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_csc: null colptr / rowval / nzval");
+      const int64_t last = idx_bytes == 8 ? reinterpret_cast<const int64_t *>(colptr)[n] : reinterpret_cast<const int32_t *>(colptr)[n];
+      if (last - index_base != nnz) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_csc: nnz must equal colptr[n] - index base");
+      if (idx_bytes == 4) {
+        cp.assign(reinterpret_cast<const int32_t *>(colptr), reinterpret_cast<const int32_t *>(colptr) + n + 1);
+        rv.assign(reinterpret_cast<const int32_t *>(rowval), reinterpret_cast<const int32_t *>(rowval) + nnz);
+      }
+    });
+    if (rc != EXPV_MI_OK) return rc;
+    static const int64_t none = 0;      // (n > 0 with no entries: the host creator wants non-null arrays it never reads)
+    const int64_t *cpp = idx_bytes == 4 ? cp.data() : reinterpret_cast<const int64_t *>(colptr);
+    const int64_t *rvp = idx_bytes == 4 ? rv.data() : reinterpret_cast<const int64_t *>(rowval);
+    return expv_mi_op_create_csc(ctx, dtype, n, cpp, nnz > 0 ? rvp : &none, nnz > 0 ? nzval : &none, index_base, out);
+  }
+  return guarded(ctx, [&] {
+    if (loc != EXPV_MI_DEVICE) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_csc: bad location");
+    ctx->use();
+    create_sparse_device(ctx, true, dtype, n, nnz, colptr, rowval, nzval, idx_bytes, index_base, out);
+  });
+}
+
+int expv_mi_op_ingest_info(expv_mi_op_t op, int64_t out[8]) {
+  if (!op || !out) return EXPV_MI_ARGUMENT_ERROR;
+  for (int i = 0; i < 8; ++i) out[i] = op->ingest[i];
+  return EXPV_MI_OK;
 }
 
 int expv_mi_op_create_dense(expv_mi_ctx_t ctx, int dtype, int64_t n, const void *A, int64_t lda, int loc,

@@ -308,6 +308,9 @@ struct Op {
   // -1 = none) and the SELL column array restated as positions in the tile's LDS image (tile row, or tile rows + ring position)
   DevBuf ring_rows, ring_cnt, ring_col, ring_soff;
   int64_t ring_col_unique = 0;      // SELL column blocks kept after sharing equal ones (slices)
+  // how the operator came to be (expv_mi_op_ingest_info): [0] 1 = from device arrays, [1] pattern bytes / [2] value bytes brought to the
+  // host, [3] whole creation / [4] ingest kernels + status read-back in microseconds, [5] 1 = plan from the plan cache
+  int64_t ingest[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool plan_cached = false;      // the ordering / patch plan came from the process-wide plan cache (capi.hip: OrderPlanCache)
   int64_t ring_sum = 0, ring_over128 = 0, ring_tiles = 0;      // sum of the ring lengths, tiles with a ring of more than 128 rows, tiles
   int ring_pad = 0;          // 0: no patch form

@@ -81,6 +81,23 @@ struct OpUpdateArgs {
                                 // [16 + d] bits of the first entry of diagonal d
 };
 template <class T> void op_scatter_values(hipStream_t s, T *dst, const T *src, const int32_t *pos, int64_t nnz);
+// ---- a caller's CSR / CSC index arrays on the device, checked and normalised there (op_ingest.hip; capi.hip: create_sparse_device) ----
+enum : unsigned long long {
+  INGEST_BAD_FIRST = 1,      // ptr[0] != index base
+  INGEST_DECREASING = 2,     // ptr[i + 1] < ptr[i] somewhere
+  INGEST_BAD_NNZ = 4,        // ptr[n] - base != the nnz the caller states
+  INGEST_BAD_INDEX = 8       // an index outside [0, n)
+};
+struct IngestStatus {          // device words, read back once
+  unsigned long long flags;
+  unsigned long long first_ptr, first_idx;      // first offending position in ptr / idx (~0: none)
+  unsigned long long desc_all, desc_starts;     // entries k >= 1 with idx[k] <= idx[k - 1]; those of them that start a row (column)
+  unsigned long long pad[3];
+};
+// ptr[n + 1], idx[nnz] of idx_bytes-wide integers (4 or 8) with index base `base` -> zero-based int32 copies ptr32[n + 1], idx32[nnz]
+// (idx32 16-byte aligned) + the status record.  No access is indexed by an unchecked value.
+void ingest_indices(hipStream_t s, int idx_bytes, const void *ptr, const void *idx, int64_t n, int64_t nnz, int base, int32_t *ptr32,
+                    int32_t *idx32, IngestStatus *st);
 // dst[i + c ld_dst] = src[idx[i] + c ld_src], i < n, c < ncols: rows of `esz`-byte elements (4, 8 or 16) picked through an index
 // vector -- the permutation of a reordered operator applied to vectors on their way in (idx = perm) and out (idx = inverse)
 void gather_rows(hipStream_t s, size_t esz, void *dst, int64_t ld_dst, const void *src, int64_t ld_src, const int32_t *idx, int64_t n,

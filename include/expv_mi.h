@@ -180,9 +180,32 @@ const char *expv_mi_prof_name(int kernel_id);
  * index_base = 1 for Julia arrays, 0 for scipy. */
 int expv_mi_op_create_csc(expv_mi_ctx_t ctx, int dtype, int64_t n, const int64_t *colptr,
                           const int64_t *rowval, const void *nzval, int index_base, expv_mi_op_t *op);
-/* CSR (what test/gpu/gputests.jl:46 hands over as CuSparseMatrixCSR); idx_bytes = 4 or 8. */
+/* CSR from HOST arrays: rowptr[n+1], colind[nnz], vals[nnz]; idx_bytes = 4 or 8 (nnz is read from rowptr[n]). */
 int expv_mi_op_create_csr(expv_mi_ctx_t ctx, int dtype, int64_t n, const void *rowptr, const void *colind,
                           const void *vals, int idx_bytes, int index_base, expv_mi_op_t *op);
+/* CSR / CSC from arrays that live where `loc` says.  loc = EXPV_MI_DEVICE is what test/gpu/gputests.jl:41-58 hands over
+ * (CuSparseMatrixCSR(A): a matrix already on the device; a torch.sparse_csr tensor, a ROCSparseMatrixCSR): all three arrays are
+ * device pointers on the context's device, the indices idx_bytes = 4 or 8 wide with index base 0 or 1, the values of `dtype`.
+ * `nnz` is the length of the index / value arrays AS THE CALLER KNOWS IT; rowptr[n] - index_base must equal it (the library does
+ * not take a buffer length from device memory it has not checked).  The arrays are read during the call only.
+ *   - The index arrays are checked on the device before anything indexes by them: rowptr[0] == index_base, rowptr non-decreasing,
+ *     rowptr[n] - index_base == nnz, every index in [0, n).  A violation returns EXPV_MI_ARGUMENT_ERROR with the host creators'
+ *     message (+ the first offending position) and nothing else has run.
+ *   - Only the normalised pattern, 4 (n + 1 + nnz) bytes, comes to the host, where the orderings and storage layouts are planned
+ *     (plan cache included).  The values go from the caller's buffer to their stored places on the device; opnorm(A, Inf),
+ *     ishermitian and the constant-diagonal test are evaluated there, as by expv_mi_op_update_values.  One exception: rows that are
+ *     not sorted and free of duplicates have their Hermitian test on the host, on a downloaded copy (expv_mi_op_ingest_info tells).
+ *   - expv_mi_op_update_values takes new values in the caller's entry order (CSR or CSC), as for host-created operators.
+ * loc = EXPV_MI_HOST: exactly expv_mi_op_create_csr / _csc on host arrays (4-byte CSC indices are widened). */
+int expv_mi_op_create_csr_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnz, const void *rowptr, const void *colind,
+                              const void *vals, int idx_bytes, int index_base, int loc, expv_mi_op_t *op);
+int expv_mi_op_create_csc_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnz, const void *colptr, const void *rowval,
+                              const void *nzval, int idx_bytes, int index_base, int loc, expv_mi_op_t *op);
+/* How a sparse operator came to be: out[0] 1 = created from device arrays; out[1] bytes of pattern brought to the host; out[2]
+ * bytes of VALUES brought to the host (0 when every row is sorted and free of duplicates); out[3] the whole creation and out[4] the
+ * ingest kernels + status read-back, in microseconds; out[5] 1 = ordering plan taken from the plan cache; out[6..7] 0.  An operator
+ * created from host arrays reports zeros. */
+int expv_mi_op_ingest_info(expv_mi_op_t op, int64_t out[8]);
 /* Dense column-major n x n (Matrix{T}); `loc` = where A lives now. */
 int expv_mi_op_create_dense(expv_mi_ctx_t ctx, int dtype, int64_t n, const void *A, int64_t lda, int loc,
                             expv_mi_op_t *op);

@@ -258,6 +258,44 @@ function patch_info(op::MIOperator)
     (patch_form = out[1] != 0, grid_row_length = out[2], tiles = out[3], longest_ring = out[4], mean_ring = out[3] > 0 ? out[5] / out[3] : 0.0)
 end
 MIOperator(A::SparseMatrixCSC{T}) where {T <: MIScalar} = MIOperator(SparseMatrixCSC{T, Int64}(A))      # (other index types: converted once)
+# A sparse matrix that is ALREADY on the device (test/gpu/gputests.jl:46: CuSparseMatrixCSR(A)): the three arrays of a CSR / CSC matrix
+# as device vectors -- the fields of a ROCSparseMatrixCSR (rowPtr, colVal, nzVal) or ROCSparseMatrixCSC (colPtr, rowVal, nzVal), wrapped
+# without a copy as MIArray{Ti, 1}(pointer, (length,), false); 1-based like every Julia sparse type.  The index arrays are checked on
+# the device, only the pattern visits the host (the orderings and storage layouts are planned there), the values stay where they are.
+# The arrays are read during the call only.  update_values!(op, nzval::MIVector) refreshes the values in the same entry order.
+function MIOperator(rowptr::MIVector{Ti}, colval::MIVector{Ti}, nzval::MIVector{T}, n::Integer;
+                    format::Symbol = :csr, index_base::Integer = 1) where {Ti <: Union{Int32, Int64}, T <: MIScalar}
+    format in (:csr, :csc) || throw(ArgumentError("MIOperator: format must be :csr or :csc"))
+    length(rowptr) == n + 1 || throw(DimensionMismatch("MIOperator: the pointer array must have n + 1 entries"))
+    length(colval) == length(nzval) || throw(DimensionMismatch("MIOperator: index and value arrays must have the same length"))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    if format == :csr
+        check(ccall((:expv_mi_op_create_csr_loc, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Ref{Ptr{Cvoid}}),
+                    ctx().h, dtype(T), n, length(nzval), rowptr.ptr, colval.ptr, nzval.ptr, sizeof(Ti), index_base, DEVICE, r), ctx().h)
+    else
+        check(ccall((:expv_mi_op_create_csc_loc, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Ref{Ptr{Cvoid}}),
+                    ctx().h, dtype(T), n, length(nzval), rowptr.ptr, colval.ptr, nzval.ptr, sizeof(Ti), index_base, DEVICE, r), ctx().h)
+    end
+    wrap_operator(T, r[])
+end
+function update_values!(op::MIOperator{T}, nzval::MIVector{T}) where {T <: MIScalar}      # new values on the device, the creation's entry order
+    length(nzval) == op.nnz || throw(DimensionMismatch("update_values!: nnz values expected"))
+    check(ccall((:expv_mi_op_update_values, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), op.h, nzval.ptr, DEVICE), ctx().h)
+    n, nz, hm, on, dt = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Cdouble}(0), Ref{Cint}(0)
+    check(ccall((:expv_mi_op_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Cint}, Ref{Cdouble}, Ref{Cint}), op.h, n, nz, hm, on, dt), ctx().h)
+    op.herm = hm[] != 0
+    op.opnorm_inf = on[]
+    op
+end
+# what operator creation brought to the host (expv_mi_op_ingest_info): for an operator made from device arrays the pattern only
+function ingest_info(op::MIOperator)
+    out = zeros(Int64, 8)
+    check(ccall((:expv_mi_op_ingest_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), op.h, out), ctx().h)
+    (from_device = out[1] != 0, pattern_bytes_to_host = out[2], value_bytes_to_host = out[3], create_s = 1.0e-6 * out[4],
+     ingest_s = 1.0e-6 * out[5], plan_cached = out[6] != 0)
+end
 function MIOperator(A::Matrix{T}) where {T <: MIScalar}
     r = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:expv_mi_op_create_dense, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{T}, Int64, Cint, Ref{Ptr{Cvoid}}),
