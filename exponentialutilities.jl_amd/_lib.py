@@ -14,6 +14,7 @@ HOST, DEVICE = 0, 1
 ORTHO_AUTO, ORTHO_MGS, ORTHO_LOWSYNC, ORTHO_PIPELINED = 0, 1, 2, 3
 PATH_FLAGS = {"modular": 1, "two_kernel": 2, "pipeline": 4, "wave": 8, "overlapped": 16, "redo_serial": 32,
               "redo_wave_off": 64, "resident": 128, "patch": 256, "pipelined_lanczos": 512}
+PATH_FA2_PIPELINED = 1024      # not a step form: which instantiation of the two-kernel step's first kernel ran (expv.last_stats["fa2_pipelined"])
 
 STATUS_NAMES = {
     0: "OK", 1: "DimensionMismatch", 2: "ArgumentError", 3: "AssertionError", 4: "SingularException",

@@ -106,7 +106,7 @@ class Context:
         """Cumulative counters of the context (expv_mi_ctx_counters)."""
         out = (C.c_int64 * 8)()
         _check(L.load().expv_mi_ctx_counters(self._h, out), self._h)
-        keys = ("krylov_steps", "factorisations", "pipeline", "overlapped", "redo_serial", "redo_wave_off", "op_applies")
+        keys = ("krylov_steps", "factorisations", "pipeline", "overlapped", "redo_serial", "redo_wave_off", "op_applies", "h_by_copy")
         return dict(zip(keys, (int(v) for v in out)))
 
     def set_pipeline_overlap(self, on=True):
@@ -915,7 +915,8 @@ def expv(t, A, b=None, *, mode="happy_breakdown", **kw):
         if kw.get("out") is None:
             w = _round_to(w, _ref_dtype(_t_dtype(t), getattr(op, "src_dtype", op.dtype), bdt))
         expv.last_stats = {"m": st.m_used, "wasbreakdown": bool(st.wasbreakdown), "matvecs": st.matvecs, "beta": st.beta,
-                           "path": [k for k, v in L.PATH_FLAGS.items() if st.path_flags & v]}
+                           "path": [k for k, v in L.PATH_FLAGS.items() if st.path_flags & v],
+                           "fa2_pipelined": bool(st.path_flags & L.PATH_FA2_PIPELINED)}
         return w
     if mode == "error_estimate":        # _expv_ee  (:145-160)
         m = kw.pop("m", min(30, op.shape[0]))

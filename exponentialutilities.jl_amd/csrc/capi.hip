@@ -1477,7 +1477,7 @@ int expv_mi_ctx_get_option(expv_mi_ctx_t ctx, const char *name, int64_t *value) 
 int expv_mi_ctx_counters(expv_mi_ctx_t ctx, int64_t out[8]) {
   if (!ctx || !out) return EXPV_MI_ARGUMENT_ERROR;
   out[0] = ctx->cnt_steps; out[1] = ctx->cnt_fact; out[2] = ctx->cnt_pipe; out[3] = ctx->cnt_live;
-  out[4] = ctx->cnt_serial_redo; out[5] = ctx->cnt_wave_redo; out[6] = ctx->cnt_opapply; out[7] = 0;
+  out[4] = ctx->cnt_serial_redo; out[5] = ctx->cnt_wave_redo; out[6] = ctx->cnt_opapply; out[7] = ctx->cnt_copy;
   return EXPV_MI_OK;
 }
 int expv_mi_ctx_selftest(expv_mi_ctx_t ctx, int64_t out[8]) {

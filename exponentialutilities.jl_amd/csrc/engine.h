@@ -154,7 +154,7 @@ struct Ctx {
   size_t ws_batch_bytes = 0;  // ... and how many bytes they hold
   void (*ws_batch_free)(void *) = nullptr;
   // cumulative counters (expv_mi_ctx_counters): what ran, and whether a bounded device wait ever expired
-  int64_t cnt_steps = 0, cnt_fact = 0, cnt_live = 0, cnt_serial_redo = 0, cnt_wave_redo = 0, cnt_opapply = 0, cnt_pipe = 0;
+  int64_t cnt_steps = 0, cnt_fact = 0, cnt_live = 0, cnt_serial_redo = 0, cnt_wave_redo = 0, cnt_opapply = 0, cnt_pipe = 0, cnt_copy = 0;
   int last_path = 0;                      // EXPV_MI_PATH_* flags of the most recent factorisation
   hipStream_t stream2 = nullptr;          // second stream + fork/join events of the overlapped pipeline
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -363,6 +363,9 @@ struct Ks {
   void *pin = nullptr;   // pinned host staging for the Hessenberg / step-state read-back
   size_t pin_bytes = 0;
   ~Ks() {
+    // b_stored comes from the context's staging spares (permute_in -> DevBuf::take_from) and would go back there: a subspace that
+    // outlives its context (back pointer cleared by orphan_children) frees it itself instead of writing into the dead context
+    if (!ctx) b_stored.home = nullptr;
     if (pin) (void)hipHostFree(pin);
     if (mbox) (void)hipHostFree(mbox);
   }
@@ -402,6 +405,12 @@ struct Ks {
   int64_t rows() const { return n + augmented; }
 };
 void ks_finish_tail(Ks &ks);   // engine_core.hip
+// a driver that asks for a deferred closing pass keeps one of these on its stack: the pass is collected on every way out, an error
+// between the factorisation and its evaluation included (ks_finish_tail clears `pending` before anything in it can throw)
+struct TailDrain {
+  Ks &k;
+  ~TailDrain() { try { ks_finish_tail(k); } catch (...) {} }
+};
 void ks_recycle(Ks &ks);       // engine_core.hip: a used subspace back to what ks_alloc leaves (same shape, storage kept)
 }  // namespace expv_mi
 struct expv_mi_ks_s : expv_mi::Ks {};

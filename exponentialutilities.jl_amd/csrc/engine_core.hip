@@ -483,6 +483,7 @@ struct ArnoldiCall {
   StepState *st = nullptr;
   double *part = nullptr, *gpart = nullptr;
   bool h_zeroed = false;
+  bool fa2_pl_used = false;      // some step's first kernel ran in the requests-up-front instantiation (path word)
   bool cont_reset_done = false; // reset_device_state() did the whole reset of a continued single-pass factorisation in one launch
   bool tail_deferred = false;   // read_back() returned at the early mailbox flag (Ks::defer_tail_req)   // first_step() zeroed this call's columns of Hdev together with the step state
   bool use_fused = false, single_red = false, use_pipe = false, use_wave = false, use_ring = false, mbox_generic = false;
@@ -1092,7 +1093,7 @@ struct ArnoldiCall {
       d.real_coeff = real_coeff;
       d.Hdev = Hd; d.ldh = ks.ldhd; d.jcol = j - 1; d.gram = ks.gram.as<T>(); d.ldg = ks.ldg; d.jrow = j - 1;
       d.hcoef = hcoef;
-      { ProfScope ps(c, EXPV_MI_K_FUSED_A); dev::fused_a2<T>(s, fa, tol); }
+      { ProfScope ps(c, EXPV_MI_K_FUSED_A); fa2_pl_used |= dev::fused_a2<T>(s, fa, tol); }
       dev::UpdateArgs<T> u{};
       u.V = V; u.ldv = ks.ldv; u.n = rows; u.y = V + (size_t)j * ks.ldv; u.yin = yb;
       if (lanczos) { u.c0 = j - 1; u.dir = -1; u.nd = (j > 1) ? 2 : 1; }
@@ -1334,7 +1335,8 @@ struct ArnoldiCall {
   c->cnt_steps += jlast - jstart + 1;
   ++c->cnt_fact;
   c->last_path = use_pipe ? (EXPV_MI_PATH_PIPELINE | (use_wave ? EXPV_MI_PATH_WAVE : 0) | (use_ring ? EXPV_MI_PATH_PATCH : 0) | (ks.pipe_live_used ? EXPV_MI_PATH_OVERLAPPED : 0) | (ks.pipe_resident_used ? EXPV_MI_PATH_RESIDENT : 0))
-                          : (use_fused ? EXPV_MI_PATH_TWO_KERNEL : EXPV_MI_PATH_MODULAR);
+                          : (use_fused ? (EXPV_MI_PATH_TWO_KERNEL | (fa2_pl_used ? EXPV_MI_PATH_FA2_PIPELINED : 0)) : EXPV_MI_PATH_MODULAR);
+  if (!from_mbox) ++c->cnt_copy;
   if (use_pipe) { ++c->cnt_pipe; if (ks.pipe_live_used) ++c->cnt_live; }
   return jlast - jstart + 1;
   }

@@ -174,6 +174,9 @@ static void phiv_timestep_T(Ctx *ctx, Op &op, int nts, double *ts, const T *B, i
     W = ws->W.as<T>();
     P = ws->P.as<T>();
     ks = ws->ks;
+    // a call that ended in an error may have left its deferred closing pass uncollected on the kept work set: collect it before H is
+    // zeroed, or the next factorisation's leading ks_finish_tail writes the failed call's H[m+1, m] / scale / breakdown into the fresh subspace
+    ks_finish_tail(*ks);
     std::fill(ks->H.begin(), ks->H.end(), 0);
     ks->gram_rows = 0;
     ks->scale_pending = false;
@@ -181,6 +184,9 @@ static void phiv_timestep_T(Ctx *ctx, Op &op, int nts, double *ts, const T *B, i
     ks->wasbreakdown = false;
     ks->beta = 0.0;
   }
+  // an error between a factorisation and its evaluation (the host exponential rejects a non-finite H) leaves no closing pass behind:
+  // drained on every way out, so that neither the context's work set nor the caller's caches carry it into the next call
+  TailDrain tail_drain{*ks};
   hipStream_t s = ctx->stream;
   HIPCHECK(hipMemcpyAsync(u, B, sizeof(T) * n, hipMemcpyDeviceToDevice, s));   // u(0) = b0
   std::vector<double> coeffs(std::max(p, 1), 1.0);
@@ -461,6 +467,10 @@ static void kiops_T(Ctx *ctx, Op &op, const double *tau_out, int ntau, int tau_n
   // the reference builds a fresh KrylovSubspace (H = zeros) per call (kiops.jl:74); the cached one must look the same:
   // arnoldi! only rewrites the window / sub-diagonal entries of the columns it produces, so the `H[1, j+1] = 1` markers
   // and entries left by a call with another iop / Lanczos setting would otherwise leak into a later call's exp(tau H)
+  // (a call that ended in an error between arnoldi_run and ks_finish_tail below -- the host exponential rejects a non-finite H -- must not
+  //  leave its closing pass pending: collected here, before H is zeroed, and drained on every way out of this call)
+  ks_finish_tail(ks);
+  TailDrain tail_drain{ks};
   std::fill(ks.H.begin(), ks.H.end(), 0);
   ks.gram_rows = 0;
   ks.scale_pending = false;

@@ -578,7 +578,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_fused_a2(FusedAArgs<T> fa, int
 
 static void plan_slices2(int64_t nslices, int max_blocks, int *nblocks, int *spw) { plan_slices(nslices, max_blocks, nblocks, spw); }
 template <class T>
-void fused_a2(hipStream_t s, const FusedAArgs<T> &a, double tol, int nbatch) {
+bool fused_a2(hipStream_t s, const FusedAArgs<T> &a, double tol, int nbatch) {
   constexpr int CH = DotChunk<T>::CH;
   constexpr int SHL = 64 * Pack<T>::N;
   const int64_t nslices = (a.aug_p || a.ext_y) ? (a.d.n + SHL - 1) / SHL : a.A.nslices;   // augmented / matrix-free: slices over all rows of the vectors
@@ -599,7 +599,7 @@ void fused_a2(hipStream_t s, const FusedAArgs<T> &a, double tol, int nbatch) {
       plan_slices2(nslices, std::max(1, resident_blocks((const void *)k)), &nb, &spw);
       hipLaunchKernelGGL(k, dim3(nb, 1), dim3(BLOCK), 0, s, a, spw, tol);
     }
-    return;
+    return true;
   }
   if (a.d.mode == DOTS_LOWSYNC) {
     auto k = k_fused_a2<T, true, CH, DOTS_WAVES>;
@@ -610,6 +610,7 @@ void fused_a2(hipStream_t s, const FusedAArgs<T> &a, double tol, int nbatch) {
     plan_slices2(nslices, std::max(1, resident_blocks((const void *)k) / nbatch), &nb, &spw);
     hipLaunchKernelGGL(k, dim3(nb, nbatch), dim3(BLOCK), 0, s, a, spw, tol);
   }
+  return false;
 }
 
 // u_{j+1} = y~ * inv - sum_i c_i V_i  ->  out;  V[:, newest] <- V[:, newest] * inv   (pure streaming, no reduction)
@@ -783,7 +784,7 @@ void permute_values(hipStream_t s, T *sell_val, int64_t sell_stride, const T *cs
   template void spmv_sell<T>(hipStream_t, int64_t, const SellView<T> &, const T *, T *, const StepState *, int, const T *); \
   template void fused_a<T>(hipStream_t, const FusedAArgs<T> &);                                                \
   template void apply_lincomb<T>(hipStream_t, const ApplyLcArgs<T> &);                                         \
-  template void fused_a2<T>(hipStream_t, const FusedAArgs<T> &, double, int);                                  \
+  template bool fused_a2<T>(hipStream_t, const FusedAArgs<T> &, double, int);                                  \
   template void update2<T>(hipStream_t, const UpdateArgs<T> &, int, int);                                      \
   template void norm_final<T>(hipStream_t, const T *, int64_t, double *, double *, StepState *, T *, int, int,  \
                               double, const BatchStrides &, int, double *);                                    \

@@ -221,7 +221,7 @@ template <class T> void fused_a(hipStream_t s, const FusedAArgs<T> &a);
 //                    Hessenberg column of step j from the rescaled sums
 //          update2 : u_{j+1} = y~/beta - sum_i c_i V_i  -> V[:, j];  V[:, j-1] <- u_j / beta   (no reduction)
 // after the loop: norm_final (beta_m, H[m+1, m], breakdown test) + finalize_last.
-template <class T> void fused_a2(hipStream_t s, const FusedAArgs<T> &a, double tol, int nbatch = 1);
+template <class T> bool fused_a2(hipStream_t s, const FusedAArgs<T> &a, double tol, int nbatch = 1);   // true: the requests-up-front instantiation ran
 template <class T> void update2(hipStream_t s, const UpdateArgs<T> &a, int newest_col, int nbatch = 1);
 template <class T>
 void norm_final(hipStream_t s, const T *x, int64_t n, double *part, double *gpart, StepState *st, T *Hdev, int ldh,

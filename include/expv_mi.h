@@ -134,7 +134,8 @@ int expv_mi_ctx_get_option(expv_mi_ctx_t ctx, const char *name, int64_t *value);
  * [2] of those on the single-pass pipeline, [3] of those with overlapped steps, [4] factorisations redone one launch after
  * the other because a bounded device wait expired (device shared with other work), [5] redone on the two-kernel step because
  * the wave form's tile wait expired, [6] operator applications outside a factorisation (phiv_timestep!'s recurrence, mul!),
- * [7] reserved.  A non-zero [4] / [5] means the overlapped / wave form was switched off for the following 64 calls. */
+ * [7] factorisations whose H and state came home by copy + stream synchronisation instead of through the host mailbox (option
+ * mailbox = 0, or a step form without one).  A non-zero [4] / [5] means the overlapped / wave form was switched off for the following 64 calls. */
 int expv_mi_ctx_counters(expv_mi_ctx_t ctx, int64_t out[8]);
 /* Device self-test: the cross-lane sums of the kernels run on v_permlane32/16_swap + DPP (no LDS round trip); this runs them
  * against the LDS-permute (shuffle) forms on random values and returns the number of lanes whose result differs in ANY bit:
@@ -148,7 +149,8 @@ enum {
   EXPV_MI_PATH_OVERLAPPED = 16, EXPV_MI_PATH_REDO_SERIAL = 32, EXPV_MI_PATH_REDO_WAVE_OFF = 64,
   EXPV_MI_PATH_RESIDENT = 128,  /* the whole factorisation ran as one resident (cooperative) kernel */
   EXPV_MI_PATH_PATCH = 256,     /* single-pass step, patch form: operator stored in a grid-patch ordering, ring recomputed */
-  EXPV_MI_PATH_PIPELINED_LANCZOS = 512      /* the opt-in pipelined Lanczos recurrence ran (EXPV_MI_ORTHO_PIPELINED) */
+  EXPV_MI_PATH_PIPELINED_LANCZOS = 512,     /* the opt-in pipelined Lanczos recurrence ran (EXPV_MI_ORTHO_PIPELINED) */
+  EXPV_MI_PATH_FA2_PIPELINED = 1024         /* two-kernel step: its first kernel ran in the requests-up-front instantiation (option fa2_pipelined; real types, SELL slots) */
 };
 const char *expv_mi_last_error(expv_mi_ctx_t ctx);
 const char *expv_mi_version(void);

@@ -131,7 +131,7 @@ function get_option(name::AbstractString)
     v[]
 end
 # cumulative counters: Krylov steps, factorisations, on the single-pass step, overlapped, redone serially, redone without the
-# wave form, operator applications outside a factorisation, reserved
+# wave form, operator applications outside a factorisation, factorisations whose H came home by copy (not the mailbox)
 function counters()
     out = zeros(Int64, 8)
     check(ccall((:expv_mi_ctx_counters, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ctx().h, out), ctx().h)

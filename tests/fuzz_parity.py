@@ -1,6 +1,18 @@
-"""Randomised parity hunt against the oracle: random sizes, element types, operator structures, calls and options.
+"""Randomised parity hunt against the oracle: random sizes, element types, operator structures, calls, call keywords and
+context options.
 Every case is derived from (seed, index), printed on failure and reproducible with  python tests/fuzz_parity.py 0 SEED INDEX.
     python tests/fuzz_parity.py SECONDS [SEED]
+Two kinds of "options".  The CALL's keywords (m, iop, ortho, ishermitian, tol ...) come from the first generator,
+default_rng([seed, index]), like everything else of a case.  The CONTEXT options that select another device form of the step
+(tests/option_forms.py: OPTION_SETS -- mailbox, dia, pipeline, fused, patch, wave, fa2_pipelined, kiops_skip_redo, batch_rounds ...)
+and the device-resident sparse presentations (torch.sparse_csr / sparse_csc, int32 / int64 indices) come from a SECOND generator,
+default_rng([seed, index, 1]), so that the cases the suite cites by (seed, index) keep reproducing:
+    FUZZ_OPTIONS=p        probability that a case draws a non-default option set / a device-resident sparse operator
+                          (default 0.5; 0 = exactly the stream of before the option axis existed)
+    FUZZ_OPTION_SET=name  replay: force the set a failing case printed as "options" (whatever FUZZ_OPTIONS was then)
+    FUZZ_DEVICE_SPARSE=x  replay: force the presentation a failing case printed as "device_sparse" ("device_csr/int32", ..., "none")
+A case with options runs on a private context from a small cache keyed by the option set; spin_limit is not drawn (an expired wait
+is a timing matter with its own subprocess test) and `resident` keeps to the sizes of test_resident_form_matches_stepwise_and_oracle.
 Test infrastructure (imports the oracle); not part of the product or of the measured path."""
 import json
 import sys
@@ -14,8 +26,15 @@ import scipy.sparse.linalg  # noqa: F401  (sp.linalg.norm)
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
 import expv_mi_loader
 from oracle import krylov_oracle as ko
+from tests.option_forms import OPTION_SETS, RESIDENT_SIZES, context_with
 
 eu = expv_mi_loader.load()
+
+_env = __import__("os").environ
+FUZZ_OPTIONS = float(_env.get("FUZZ_OPTIONS", "0.5"))
+FUZZ_OPTION_SET = _env.get("FUZZ_OPTION_SET", "")
+FUZZ_DEVICE_SPARSE = _env.get("FUZZ_DEVICE_SPARSE", "")
+OPTION_NAMES = [k for k in OPTION_SETS if k != "default"]
 
 
 FOCUS = __import__("os").environ.get("FUZZ_FOCUS", "")      # "complex_windows": complex element types, banded / grid / wide-band operators, m in 16..40 (round 5's new kernels)
@@ -116,12 +135,42 @@ def _limited(f, seconds):
 
 
 _ACTX = []
+_OCTX = {}          # (option set, async outputs) -> private context; insertion-ordered, the oldest dropped beyond _OCTX_MAX
+_OCTX_MAX = 4
 
 
 def _async_ctx():
     if not _ACTX:
         _ACTX.append(eu.Context(async_outputs=True))
     return _ACTX[0]
+
+
+def _option_ctx(oname, async_outputs=False):
+    """the private context of an option set (options set before any operator exists on it); None = the default context"""
+    if oname == "default":
+        return _async_ctx() if async_outputs else None
+    key = (oname, async_outputs)
+    if key not in _OCTX:
+        while len(_OCTX) >= _OCTX_MAX:
+            _OCTX.pop(next(iter(_OCTX)))
+        _OCTX[key] = context_with(eu, OPTION_SETS[oname], async_outputs=async_outputs)
+    return _OCTX[key]
+
+
+def _draw_second_axis(seed, index):
+    """(option set, device-resident sparse presentation) of a case, from the second generator: always the same three draws"""
+    rng2 = np.random.default_rng([seed, index, 1])
+    u, oname = rng2.random(), OPTION_NAMES[int(rng2.integers(len(OPTION_NAMES)))]
+    v, dsp = rng2.random(), "device_%s/%s" % (("csr", "csc")[int(rng2.integers(2))], ("int32", "int64")[int(rng2.integers(2))])
+    if not u < FUZZ_OPTIONS:
+        oname = "default"
+    if not v < 0.25 * FUZZ_OPTIONS:
+        dsp = "none"
+    if FUZZ_OPTION_SET:
+        oname = FUZZ_OPTION_SET
+    if FUZZ_DEVICE_SPARSE:
+        dsp = FUZZ_DEVICE_SPARSE
+    return oname, dsp
 
 
 def _np(x):
@@ -165,6 +214,12 @@ def one_case(seed, index, verbose=False):
     if n > 5000 and call not in ("expv", "arnoldi", "expv_complex_t", "phiv", "subspace_reuse", "update_values"):
         call = "expv"                 # (large cases: the calls whose oracle stays cheap)
     desc = {"seed": seed, "index": index, "T": T.name, "n": n, "operator": kind, "m": m, "iop": iop, "hermitian": herm, "call": str(call), "ortho": ortho}
+    oname, dsp = _draw_second_axis(seed, index)
+    if "resident" in OPTION_SETS[oname] and n not in RESIDENT_SIZES:
+        oname = "default"
+    ctx = _option_ctx(oname)          # None: the default context, as before
+    if oname != "default":
+        desc["options"] = oname
     if verbose:
         print(desc, flush=True)
     tol = 3e-4 if single else 1e-10
@@ -192,6 +247,14 @@ def one_case(seed, index, verbose=False):
         import torch                  # a device-resident dense operator, row-major (torch's default) or column-major
         Ad = torch.as_tensor(A, device="cuda")
         Ain = Ad if rng.random() < 0.5 else Ad.t().contiguous().t()
+    if dsp != "none" and sp.issparse(A):
+        import torch                  # CSR / CSC arrays that live on the device (taken where they are: expv_mi_op_create_csr_loc / _csc_loc)
+        fmt, idx = dsp[len("device_"):].split("/")
+        M = A.tocsr() if fmt == "csr" else A.tocsc()
+        M.sort_indices()
+        mk = torch.sparse_csr_tensor if fmt == "csr" else torch.sparse_csc_tensor
+        Ain = mk(torch.as_tensor(M.indptr.astype(idx)), torch.as_tensor(M.indices.astype(idx)), torch.as_tensor(M.data.copy()), size=M.shape).to("cuda")
+        desc["device_sparse"] = dsp
     as64 = lambda x: np.asarray(x).astype(T64 if np.asarray(x).dtype.kind == "c" or cplx else np.float64)
     def rel(a, r):
         a, r = np.asarray(a), np.asarray(r)
@@ -209,15 +272,24 @@ def one_case(seed, index, verbose=False):
         # zero starting vector: arnoldi! returns at iszero(beta) (arnoldi.jl:366) with V `undef`; what phiv / the time steppers make of
         # that (0 x undef, x / 0.0) is not defined behaviour -- expv and arnoldi themselves are compared (zero result, m = 0 rules)
         call = desc["call"] = "expv"
+    # a case with options: the operator its call uses is created on the private context (dia / patch / reorder / stencil act at
+    # creation) -- only that one; update_values / matrix_free / batch / async_device make their own from ctx
+    Aop = A
+    if ctx is not None and call in ("expv", "expv_complex_t", "phiv", "expv_timestep", "phiv_timestep", "kiops"):
+        Ain = eu.MIOperator(Ain, ctx)
+    elif ctx is not None and call in ("arnoldi", "subspace_reuse", "continuation", "caches", "phiv_correct", "error_estimate"):
+        Aop = eu.MIOperator(A, ctx)
     if call == "expv":
         w = eu.expv(tq, Ain, bin_, ortho=ortho, **kw)
         err = rel(_np(w), ko.expv(tq, A64, b64, **kw))
         extra = {"t": tq}
+        desc["path"] = list(eu.expv.last_stats["path"])
     elif call == "expv_complex_t":
         w = eu.expv(0.3 - 0.4j, Ain, bin_, **kw)
         err = rel(_np(w), ko.expv(0.3 - 0.4j, A64, b64, **kw))
+        desc["path"] = list(eu.expv.last_stats["path"])
     elif call == "arnoldi":
-        Ks = eu.arnoldi(A, b, ortho=ortho, **kw)
+        Ks = eu.arnoldi(Aop, b, ortho=ortho, **kw)
         Ko = ko.arnoldi(A64, b64, **kw)
         extra = {"m_dev": int(Ks.m), "m_ref": int(Ko.m)}
         md = int(Ks.m)
@@ -356,12 +428,12 @@ def one_case(seed, index, verbose=False):
         tol = 1e-9
     elif call == "subspace_reuse":
         # one KrylovSubspace through several factorisations: growing / shrinking m, other starting vectors, Lanczos <-> Arnoldi
-        Ks = eu.KrylovSubspace(T, None, n, max(1, m // 2))
+        Ks = eu.KrylovSubspace(T, None, n, max(1, m // 2), 0, ctx)
         for rep in range(int(rng.integers(2, 5))):
             mm = int(rng.integers(1, m + 1))
             hh = herm and bool(rng.integers(0, 2))
             bb = (rng.standard_normal(n) + (1j * rng.standard_normal(n) if cplx else 0)).astype(T)
-            eu.arnoldi_(Ks, A, bb, m=mm, iop=iop, ishermitian=hh, ortho=ortho)
+            eu.arnoldi_(Ks, Aop, bb, m=mm, iop=iop, ishermitian=hh, ortho=ortho)
             w = eu.expv(0.6, Ks)
             err = max(err, rel(w, ko.expv(0.6, A64, bb.astype(T64), m=mm, iop=iop, ishermitian=hh)))
     elif call == "continuation":
@@ -370,11 +442,11 @@ def one_case(seed, index, verbose=False):
             return desc, 0.0, tol, {"skipped": "continuation is exercised on the Arnoldi path"}
         m2 = max(2, m)
         m1 = int(rng.integers(1, m2))
-        Ks = eu.KrylovSubspace(T, None, n, m2)
-        eu.arnoldi_(Ks, A, b, m=m1, iop=iop, ishermitian=False, ortho=ortho)
+        Ks = eu.KrylovSubspace(T, None, n, m2, 0, ctx)
+        eu.arnoldi_(Ks, Aop, b, m=m1, iop=iop, ishermitian=False, ortho=ortho)
         if Ks.wasbreakdown:
             return desc, 0.0, tol, {"skipped": "breakdown before the continuation point"}
-        eu.arnoldi_(Ks, A, b, m=m2, iop=iop, ishermitian=False, ortho=ortho, init=m1)
+        eu.arnoldi_(Ks, Aop, b, m=m2, iop=iop, ishermitian=False, ortho=ortho, init=m1)
         w = eu.expv(0.6, Ks)
         err = rel(w, ko.expv(0.6, A64, b64, m=m2, iop=iop, ishermitian=False))
         extra = {"m1": m1, "m2": m2}
@@ -382,7 +454,7 @@ def one_case(seed, index, verbose=False):
     elif call == "update_values":
         if not sp.issparse(A):
             return desc, 0.0, tol, {"skipped": "value updates are for sparse operators"}
-        op = eu.MIOperator(A.copy())
+        op = eu.MIOperator(A.copy(), ctx)
         w0 = eu.expv(0.7, op, b, **kw)
         A2 = A.copy()
         A2.data = (A2.data * (1 + 0.1 * rng.standard_normal(A2.nnz))).astype(T)
@@ -395,7 +467,7 @@ def one_case(seed, index, verbose=False):
         if single or n > 5000:
             return desc, 0.0, tol, {"skipped": "matrix-free case kept to 64-bit, small n"}
         Ad = torch.as_tensor(A64.toarray() if sp.issparse(A64) else A64, device="cuda")
-        op = eu.MIOperator(None, matvec=lambda x: Ad @ x, shape=(n, n), dtype=T, ishermitian=herm)
+        op = eu.MIOperator(None, ctx, matvec=lambda x: Ad @ x, shape=(n, n), dtype=T, ishermitian=herm)
         w = eu.expv(0.7, op, b, **kw)
         err = rel(w, ko.expv(0.7, A64, b64, **kw))
     elif call == "batch":
@@ -407,7 +479,7 @@ def one_case(seed, index, verbose=False):
         vals = np.stack([P.data * (1 + 0.05 * rng.standard_normal(P.nnz)) for _ in range(nprob)]).astype(T)
         Bm = np.asfortranarray((rng.standard_normal((n, nprob)) + (1j * rng.standard_normal((n, nprob)) if cplx else 0)).astype(T))
         mb = min(m, 30)
-        W = np.asarray(eu.expv_batch(0.7, P, vals, Bm, m=mb, iop=iop))
+        W = np.asarray(eu.expv_batch(0.7, P, vals, Bm, m=mb, iop=iop, ctx=ctx))
         extra["batch_problems"] = []
         for q in range(nprob):
             Aq = P.copy()
@@ -420,8 +492,8 @@ def one_case(seed, index, verbose=False):
         import torch
         if n > 200000:
             return desc, 0.0, tol, {"skipped": "size"}
-        ctx = _async_ctx()
-        op = eu.MIOperator(A, ctx)
+        actx = _option_ctx(oname, async_outputs=True)
+        op = eu.MIOperator(A, actx)
         tdt = {"float32": torch.float32, "float64": torch.float64, "complex64": torch.complex64, "complex128": torch.complex128}[T.name]
         nb = int(rng.integers(1, 4))
         bs = [(rng.standard_normal(n) + (1j * rng.standard_normal(n) if cplx else 0)).astype(T) for _ in range(nb)]
@@ -429,7 +501,7 @@ def one_case(seed, index, verbose=False):
         outs = [torch.empty(n, dtype=tdt, device="cuda") for _ in range(nb)]
         for x, o in zip(bd, outs):
             eu.expv(0.7, op, x, out=o, ortho=ortho, **kw)
-        ctx.sync()
+        actx.sync()
         for x, o in zip(bs, outs):
             err = max(err, rel(o.cpu().numpy(), ko.expv(0.7, A64, x.astype(T64), **kw)))
     elif call == "caches":
@@ -439,7 +511,7 @@ def one_case(seed, index, verbose=False):
         mm = max(2, min(m, 20))
         nrep = int(rng.integers(2, 4))
         pmax = 3
-        caches = eu.timestep_caches(b, mm + 3 * nrep, pmax)       # (the reference asserts the cache dimensions: sized for the largest call)
+        caches = eu.timestep_caches(b, mm + 3 * nrep, pmax, ctx)       # (the reference asserts the cache dimensions: sized for the largest call)
         for rep in range(nrep):
             p = pmax if rep == 0 else int(rng.integers(0, pmax + 1))
             B = (rng.standard_normal((n, p + 1)) + (1j * rng.standard_normal((n, p + 1)) if cplx else 0)).astype(T)
@@ -449,7 +521,7 @@ def one_case(seed, index, verbose=False):
             U = np.empty((n, len(ts)), dtype=T, order="F")
             fr = lambda: ko.phiv_timestep(ts.copy(), A64, (B if p else B[:, 0]).astype(T64), tol=tolk, m=mrep, iop=iop, adaptive=True)
             try:
-                eu.phiv_timestep_(U, ts.copy(), A, B if p else B[:, 0], tol=tolk, m=mrep, iop=iop, adaptive=True, caches=caches)
+                eu.phiv_timestep_(U, ts.copy(), Aop, B if p else B[:, 0], tol=tolk, m=mrep, iop=iop, adaptive=True, caches=caches)
             except (ValueError, RuntimeError) as e:
                 if "did not reach the tolerance" in str(e):
                     # The device's documented stop after 1000 equal proposals: the reference's controller has no such stop and
@@ -484,7 +556,7 @@ def one_case(seed, index, verbose=False):
         Ko = ko.arnoldi(A64, b64, m=m, iop=iop)
         if Ko.wasbreakdown or Ko.m < m:
             return desc, 0.0, tol, {"skipped": "the correction uses v_{m+1} and H[m+1, m]: rounding noise (or NaN) after a happy breakdown"}
-        W, e1 = eu.phiv(0.5, A, b, k, m=m, iop=iop, correct=True, errest=True)
+        W, e1 = eu.phiv(0.5, Aop, b, k, m=m, iop=iop, correct=True, errest=True)
         Wo, e2 = ko.phiv(0.5, A64, b64, k, m=m, iop=iop, correct=True, errest=True)
         err = rel(W, Wo)
         if np.isfinite(e2) and e2 > 1e-10 * max(float(np.linalg.norm(Wo)), 1e-300) and not single:
@@ -492,7 +564,7 @@ def one_case(seed, index, verbose=False):
     else:
         if not herm:
             return desc, 0.0, tol, {"skipped": "error estimate needs a Hermitian operator here"}
-        w = eu.expv(0.7, A, b, m=max(m, 3), mode="error_estimate", rtol=1e-6 if not single else 1e-4)
+        w = eu.expv(0.7, Aop, b, m=max(m, 3), mode="error_estimate", rtol=1e-6 if not single else 1e-4)
         wo = ko.expv(0.7, A64, b64, m=max(m, 3), mode="error_estimate", rtol=1e-6 if not single else 1e-4)
         err = rel(w, wo)
         tol = 1e-9 if not single else 5e-4
@@ -570,6 +642,7 @@ def main():
     index = int(sys.argv[3]) if False else 0
     fails = 0
     worst = {}
+    options_seen, paths_seen = {}, {}
     import signal
 
     def on_alarm(sig, frm):
@@ -584,6 +657,9 @@ def main():
         try:
             desc, err, tol, extra = one_case(seed, index)
             key = (desc["call"], "32" if desc["T"] in ("float32", "complex64") else "64")
+            options_seen[desc.get("options", "default")] = options_seen.get(desc.get("options", "default"), 0) + 1
+            for word in desc.get("path", ()):
+                paths_seen[word] = paths_seen.get(word, 0) + 1
             if "skipped" not in extra:
                 worst[key] = max(worst.get(key, 0.0), err if np.isfinite(err) else 1e300)
             if not err <= tol:
@@ -597,7 +673,8 @@ def main():
     signal.alarm(0)
     import faulthandler
     faulthandler.dump_traceback_later(60, exit=True)      # (a hang while the interpreter tears down is reported, not waited for)
-    print(json.dumps({"cases": index - start, "failures": fails, "seconds": round(time.time() - t0, 1),
+    print(json.dumps({"cases": index - start, "failures": fails, "seconds": round(time.time() - t0, 1), "seed": seed, "fuzz_options": FUZZ_OPTIONS,
+                      "options_seen": dict(sorted(options_seen.items())), "paths_seen": dict(sorted(paths_seen.items())),
                       "worst_by_call": {"%s/%s" % k: v for k, v in sorted(worst.items())}}), flush=True)
     sys.exit(1 if fails else 0)
 

@@ -869,12 +869,37 @@ def test_randomised_parity_hunt_short():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, FUZZ_LARGE="0.02")
+    env = dict(os.environ, FUZZ_LARGE="0.02", FUZZ_OPTIONS="0")      # (FUZZ_OPTIONS=0: the stream this test has always run, on the default context)
+    env.pop("FUZZ_OPTION_SET", None)
+    env.pop("FUZZ_DEVICE_SPARSE", None)
     p = subprocess.run([sys.executable, os.path.join(root, "tests", "fuzz_parity.py"), "6", "20260928"], cwd=root, capture_output=True, text=True,
                        timeout=600, env=env)
     last = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     r = json.loads(last)
     assert p.returncode == 0 and r["failures"] == 0 and r["cases"] > 100, p.stdout[-3000:] + p.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_randomised_parity_hunt_short_with_context_options():
+    """The same six seconds with every case on a non-default option set of tests/option_forms.py (FUZZ_OPTIONS=1: a private context per
+    set, a quarter of the sparse operators handed over as device-resident CSR / CSC tensors): no failure, no exception, and the
+    cases reached every step form -- the path words of the expv calls among them.  profiles/fuzz_parity_context_options.txt has the long run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, FUZZ_LARGE="0.02", FUZZ_OPTIONS="1")
+    env.pop("FUZZ_OPTION_SET", None)
+    env.pop("FUZZ_DEVICE_SPARSE", None)
+    p = subprocess.run([sys.executable, os.path.join(root, "tests", "fuzz_parity.py"), "6", "20260928"], cwd=root, capture_output=True, text=True,
+                       timeout=600, env=env)
+    last = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
+    r = json.loads(last)
+    assert p.returncode == 0 and r["failures"] == 0 and r["cases"] > 100, p.stdout[-3000:] + p.stderr[-2000:]
+    assert "default" not in r["options_seen"] or r["options_seen"]["default"] < r["cases"] // 10, r["options_seen"]      # (default: only `resident` off its sizes)
+    for word in ("pipeline", "overlapped", "wave", "patch", "two_kernel", "modular"):
+        assert r["paths_seen"].get(word, 0) > 0, (word, r["paths_seen"])
 
 
 # ------------------------------------------------------------------ reordered operators (reorder.h) --------
