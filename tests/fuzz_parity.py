@@ -11,6 +11,9 @@ default_rng([seed, index, 1]), so that the cases the suite cites by (seed, index
                           (default 0.5; 0 = exactly the stream of before the option axis existed)
     FUZZ_OPTION_SET=name  replay: force the set a failing case printed as "options" (whatever FUZZ_OPTIONS was then)
     FUZZ_DEVICE_SPARSE=x  replay: force the presentation a failing case printed as "device_sparse" ("device_csr/int32", ..., "none")
+A THIRD generator, default_rng([seed, index, 2]), replaces m (1 .. 40 from the first) in a small share of the cases
+(BOUNDARY_M_SHARE) by a value either side of the single-pass and the two-kernel window (BOUNDARY_M: 31 .. 33, 63 .. 66) -- the
+compiled-in limits of csrc/kernels.h, tests/test_gpu_limits.py; every other draw of every case stays what it was.
 A case with options runs on a private context from a small cache keyed by the option set; spin_limit is not drawn (an expired wait
 is a timing matter with its own subprocess test) and `resident` keeps to the sizes of test_resident_form_matches_stepwise_and_oracle.
 Test infrastructure (imports the oracle); not part of the product or of the measured path."""
@@ -173,6 +176,19 @@ def _draw_second_axis(seed, index):
     return oname, dsp
 
 
+# Krylov dimensions either side of the single-pass window (PIPE_CH = 32: 31 / 32 columns) and of the two-kernel window (LOWSYNC_MAX =
+# 64), csrc/kernels.h -- tests/test_gpu_limits.py has the fixed cases; here a small share of the draws lands on them too
+BOUNDARY_M = (31, 32, 33, 63, 64, 65, 66)
+BOUNDARY_M_SHARE = 0.03
+
+
+def _draw_boundary_m(seed, index):
+    """0, or the boundary value that replaces the case's m -- from a generator of its own, so that every other draw of every case
+    (and with them the cases pinned by (seed, index) in the suite) stays what it was"""
+    rng3 = np.random.default_rng([seed, index, 2])
+    return int(rng3.choice(BOUNDARY_M)) if rng3.random() < BOUNDARY_M_SHARE else 0
+
+
 def _np(x):
     return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
 
@@ -207,6 +223,8 @@ def one_case(seed, index, verbose=False):
     if FOCUS == "complex_windows":
         m = int(rng.integers(16, 41))
         iop = int(rng.choice([0, 0, 0, 17, 24, 31]))
+    elif _draw_boundary_m(seed, index):
+        m = _draw_boundary_m(seed, index)
     herm = kind in ("symmetric_banded", "hermitian_dense", "grid2d_symmetric", "wide_band_symmetric") and bool(rng.integers(0, 2))
     call = rng.choice(["expv", "expv", "arnoldi", "phiv", "expv_timestep", "phiv_timestep", "expv_complex_t", "kiops", "error_estimate",
                        "subspace_reuse", "continuation", "update_values", "matrix_free", "batch", "phiv_correct", "async_device", "caches"])
