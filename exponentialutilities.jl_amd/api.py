@@ -30,6 +30,7 @@ __all__ = [
     "Context", "default_context", "MIOperator", "DeviceArray", "KrylovSubspace", "arnoldi", "arnoldi_",
     "lanczos_", "expv", "expv_", "phiv", "phiv_", "expv_timestep", "expv_timestep_", "phiv_timestep",
     "phiv_timestep_", "kiops", "timestep_caches", "expv_batch", "expv_batch_multi", "RcclComm", "rccl_available", "rccl_unique_id", "ExpvMIError", "DimensionMismatch", "host_expm",
+    "exponential", "exponential_", "mul_",
     "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
 ]
 
@@ -77,6 +78,7 @@ class Context:
         self._finalizer = weakref.finalize(self, lib.expv_mi_ctx_destroy, h)
         # async_outputs: device-resident results are stream-ordered (valid after ctx.sync() or for later work on
         # the context's stream) instead of complete when a call returns
+        self._async_outputs = bool(async_outputs)
         if async_outputs:
             _check(lib.expv_mi_ctx_set_async_outputs(h, 1))
 
@@ -86,6 +88,7 @@ class Context:
     def set_async_outputs(self, on=True):
         """Device-resident results stream-ordered (True) or complete on return (False, the C-ABI default)."""
         _check(L.load().expv_mi_ctx_set_async_outputs(self._h, int(bool(on))), self._h)
+        self._async_outputs = bool(on)
 
     def set_option(self, name, value):
         """Engine option of this context by name (expv_mi_ctx_set_option; see include/expv_mi.h for the list)."""
@@ -1250,6 +1253,145 @@ class RcclComm:
     def destroy(self):
         if self._finalizer.alive:
             self._finalizer()
+
+
+# ---------------------------------------------------------------------------------------------
+# dense matrices on the device: exponential!(A) for a GPU array (exp.jl:56-58), mul!(C, A, B, alpha, beta)
+# ---------------------------------------------------------------------------------------------
+_DENSE_KINDS = "float32 / float64 / complex64 / complex128"
+
+
+def _dense_np_dtype(x):
+    """element type of a dense matrix argument; TypeError for anything but the four BlasFloats (integers included)"""
+    if isinstance(x, DeviceArray):
+        dt = x.dtype
+    elif _is_torch(x):
+        import torch
+        dt = {torch.float64: np.dtype(np.float64), torch.complex128: np.dtype(np.complex128),
+              torch.float32: np.dtype(np.float32), torch.complex64: np.dtype(np.complex64)}.get(x.dtype)
+        if dt is None:
+            raise TypeError(f"dense matrix entries must be {_DENSE_KINDS}, not {x.dtype}")
+        return dt
+    else:
+        dt = np.asarray(x).dtype
+    if dt not in _HOST_CODES:
+        raise TypeError(f"dense matrix entries must be {_DENSE_KINDS}, not {dt}")
+    return np.dtype(dt)
+
+
+def _square(shape, what):
+    if len(shape) != 2 or shape[0] != shape[1]:
+        raise DimensionMismatch(f"{what}: matrix is not square: dimensions are {tuple(shape)}")
+    return int(shape[0])
+
+
+_EXPM_INFO = ("order", "squarings", "row_exchanges", "microseconds")
+
+
+def exponential_(A, ctx=None, return_info=False):
+    """exponential!(A) for a dense matrix, computed on the device whatever its size (exp.jl:56-58 -> ExpMethodHigham2005(false),
+    no balancing; expv_mi_expm).  A: a 2-D torch tensor on the GPU or a DeviceArray (used in place) or a numpy array (staged
+    through HBM, result copied back).  Row-major (C-contiguous) storage is passed as it is -- exp(A') = exp(A)' --, column-major
+    storage with its own leading dimension, any other stride pattern through a copy.  Returns A (and, with return_info, a dict:
+    Pade order, squarings, row exchanges of the LU, microseconds)."""
+    dt = _dense_np_dtype(A)
+    shape = tuple(A.shape)
+    n = _square(shape, "exponential!")
+    info = (C.c_int64 * 8)()
+
+    def run(c, ptr, lda, loc):
+        _check(L.load().expv_mi_expm(c._h, _code(dt), n, ptr, max(int(lda), n, 1), loc, info), c._h)
+
+    if isinstance(A, DeviceArray):
+        run(ctx or A.ctx, A.ptr, n, L.DEVICE)
+    elif _is_torch(A):
+        if not A.is_cuda:
+            raise TypeError("torch tensors must live on the GPU (or pass a numpy array)")
+        c = ctx or default_context()
+        if n > 0:
+            if n == 1 or (A.stride(1) == 1 and A.stride(0) >= n):         # row-major: the transpose, column-major
+                _torch_ready(A)
+                run(c, A.data_ptr(), A.stride(0) if n > 1 else 1, L.DEVICE)
+            elif A.stride(0) == 1 and A.stride(1) >= n:
+                _torch_ready(A)
+                run(c, A.data_ptr(), A.stride(1), L.DEVICE)
+            else:
+                tmp = A.contiguous()
+                _torch_ready(tmp)
+                run(c, tmp.data_ptr(), n, L.DEVICE)
+                A.copy_(tmp)
+    else:
+        if not isinstance(A, np.ndarray):
+            raise TypeError("exponential_ works in place: pass a numpy array, a torch GPU tensor or a DeviceArray")
+        c = ctx or default_context()
+        if n > 0:
+            if (A.flags.f_contiguous or A.flags.c_contiguous) and A.flags.writeable:
+                run(c, A.ctypes.data, n, L.HOST)
+            else:
+                tmp = np.array(A, order="F", copy=True)
+                run(c, tmp.ctypes.data, n, L.HOST)
+                A[...] = tmp
+    if return_info:
+        return A, dict(zip(_EXPM_INFO, (int(v) for v in info[:4])))
+    return A
+
+
+def exponential(A, ctx=None, return_info=False):
+    """exponential(A): a new array of A's kind holding exp(A) (see exponential_)."""
+    _dense_np_dtype(A)
+    if isinstance(A, DeviceArray):
+        B = DeviceArray.from_host(A.to_host(), A.ctx)
+    elif _is_torch(A):
+        B = A.clone()
+    else:
+        B = np.array(A, order="F", copy=True)
+    return exponential_(B, ctx=ctx, return_info=return_info)
+
+
+def _dense_dev_arg(x, dt, what):
+    """(pointer, leading dimension, shape) of a column-major device matrix"""
+    if isinstance(x, DeviceArray):
+        if x.dtype != dt or x.ndim != 2:
+            raise TypeError(f"mul_: {what} must be a 2-D device array of dtype {dt}")
+        return x.ptr, max(x.shape[0], 1), x.shape, x
+    if not (_is_torch(x) and x.is_cuda):
+        raise TypeError(f"mul_: {what} must be a torch tensor on the GPU or a DeviceArray")
+    if x.dim() != 2 or _dense_np_dtype(x) != dt:
+        raise TypeError(f"mul_: {what} must be a 2-D tensor of dtype {dt}")
+    return None, None, tuple(x.shape), x
+
+
+def mul_(Cm, A, B, alpha=1, beta=0, ctx=None):
+    """mul!(C, A, B, alpha, beta): C = alpha A B + beta C for matrices on the device, on the matrix cores (expv_mi_gemm).  torch
+    tensors in column-major storage (e.g. torch.empty(n, m).t()) are used in place; row-major A / B are copied, a row-major C is
+    refused.  C must not alias A or B."""
+    dt = _dense_np_dtype(Cm)
+    args = [_dense_dev_arg(x, dt, w) for x, w in ((Cm, "C"), (A, "A"), (B, "B"))]
+    (m, n), (ma, k), (kb, nb) = (tuple(int(v) for v in a[2]) for a in args)
+    if ma != m or kb != k or nb != n:
+        raise DimensionMismatch(f"mul!: C is {m}x{n}, A is {ma}x{k}, B is {kb}x{nb}")
+    alpha, beta = complex(alpha), complex(beta)
+    if dt.kind != "c" and (alpha.imag != 0 or beta.imag != 0):
+        raise TypeError("InexactError: complex scalar with a real element type")
+    ptrs, keep = [], []
+    for i, (ptr, ld, shape, x) in enumerate(args):
+        if ptr is None:
+            if not (x.stride(0) == 1 and (shape[1] <= 1 or x.stride(1) >= max(shape[0], 1))) and min(shape) > 0:
+                if i == 0:
+                    raise TypeError("output matrix must be column-major (e.g. torch.empty(n, m).t())")
+                x = x.t().contiguous().t()
+            keep.append(x)
+            ptr, ld = x.data_ptr(), (x.stride(1) if shape[1] > 1 else max(shape[0], 1))
+        ptrs.append((ptr, max(int(ld), 1)))
+    tens = [x for x in keep if _is_torch(x)]
+    if tens:
+        _torch_ready(*tens)
+    c = ctx or (Cm.ctx if isinstance(Cm, DeviceArray) else default_context())
+    _check(L.load().expv_mi_gemm(c._h, _code(dt), m, n, k, alpha.real, alpha.imag, ptrs[1][0], ptrs[1][1], ptrs[2][0], ptrs[2][1],
+                                 beta.real, beta.imag, ptrs[0][0], ptrs[0][1]), c._h)
+    if not getattr(c, "_async_outputs", False):      # stream-ordered on the library's stream: torch reads C on its own
+        c.sync()
+    return Cm
 
 
 def _host_dtype(*dts):

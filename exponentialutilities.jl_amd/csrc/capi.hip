@@ -1,5 +1,6 @@
 // capi.hip -- the extern "C" surface declared in include/expv_mi.h.  Nothing here throws.
 #include <algorithm>
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <mutex>
@@ -1413,6 +1414,7 @@ int expv_mi_ctx_create(int device_id, void *stream, expv_mi_ctx_t *out) {
     std::unique_ptr<expv_mi_ctx_s> c(new expv_mi_ctx_s());
     c->device = device_id;
     c->opt = Options::from_env();
+    if (const char *e = std::getenv("EXPV_MI_DENSE_TILE")) c->dense_tile = std::atoi(e);      // developer A/B of the dense product's tiles
     HIPCHECK(hipSetDevice(device_id));
     if (stream) {
       c->stream = reinterpret_cast<hipStream_t>(stream);
@@ -1437,6 +1439,7 @@ int expv_mi_ctx_destroy(expv_mi_ctx_t ctx) {
   if (ctx->ws_ts && ctx->ws_ts_free) ctx->ws_ts_free(ctx->ws_ts);
   if (ctx->ws_batch_pat && ctx->ws_batch_pat_free) ctx->ws_batch_pat_free(ctx->ws_batch_pat);
   if (ctx->ws_batch && ctx->ws_batch_free) ctx->ws_batch_free(ctx->ws_batch);
+  if (ctx->ws_dense && ctx->ws_dense_free) ctx->ws_dense_free(ctx->ws_dense);
   for (auto &sp : ctx->stage_spares) (void)hipFree(sp.p);
   ctx->stage_spares.clear();
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -1958,6 +1961,45 @@ int expv_mi_gemv_block(expv_mi_ctx_t ctx, int dtype, int64_t nrows, int64_t ncol
       dev::gemv_dense<T>(ctx->stream, nrows, reinterpret_cast<const T *>(A), lda, reinterpret_cast<const T *>(x), reinterpret_cast<T *>(y),
                          reinterpret_cast<T *>(scratch), nsplit, nullptr, 0, ncols);
     });
+  });
+}
+
+// ------------------------------------------------------------------ dense matrices on the device ----------
+int expv_mi_expm(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t info[8]) {
+  return guarded(ctx, [&] {
+    const auto t0 = std::chrono::steady_clock::now();
+    check_device_dtype(dtype, "expm");
+    if (loc != EXPV_MI_HOST && loc != EXPV_MI_DEVICE) fail(EXPV_MI_ARGUMENT_ERROR, "expm: unknown loc");
+    if (n < 0 || lda < n) fail(EXPV_MI_ARGUMENT_ERROR, "expm: bad n / lda");
+    if (info) std::fill(info, info + 8, (int64_t)0);
+    if (n == 0) return;
+    if (!A) fail(EXPV_MI_ARGUMENT_ERROR, "expm: null pointer");
+    if (!ctx) fail(EXPV_MI_ARGUMENT_ERROR, "expm: null context");
+    if (n > 65535) fail(EXPV_MI_UNSUPPORTED, "expm: n > 65535");
+    ctx->use();
+    const size_t esz = dtype_size(dtype);
+    DevBuf stage;
+    int64_t ldd = lda;
+    void *Ad = const_cast<void *>(stage_in_2d(ctx, A, loc, n, n, lda, esz, stage, &ldd));
+    dense_expm_run(ctx, dtype, n, Ad, ldd, info);
+    if (loc == EXPV_MI_HOST) copy_out_2d(ctx, A, loc, lda, Ad, ldd, n, n, esz);
+    else if (!ctx->async_out) HIPCHECK(hipStreamSynchronize(ctx->stream));
+    if (info) info[3] = (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+  });
+}
+
+int expv_mi_gemm(expv_mi_ctx_t ctx, int dtype, int64_t m, int64_t n, int64_t k, double alpha_re, double alpha_im, const void *A, int64_t lda,
+                 const void *B, int64_t ldb, double beta_re, double beta_im, void *C, int64_t ldc) {
+  return guarded(ctx, [&] {
+    check_device_dtype(dtype, "gemm");
+    if (m < 0 || n < 0 || k < 0 || lda < m || ldb < k || ldc < m) fail(EXPV_MI_ARGUMENT_ERROR, "gemm: bad m / n / k / leading dimension");
+    if (!dtype_is_complex(dtype) && (alpha_im != 0.0 || beta_im != 0.0)) fail(EXPV_MI_ARGUMENT_ERROR, "gemm: complex scalar with a real element type");
+    if (m == 0 || n == 0) return;
+    if (!C || (k > 0 && (!A || !B))) fail(EXPV_MI_ARGUMENT_ERROR, "gemm: null pointer");
+    if (!ctx) fail(EXPV_MI_ARGUMENT_ERROR, "gemm: null context");
+    if (n > (int64_t)65535 * 64) fail(EXPV_MI_UNSUPPORTED, "gemm: n too large");
+    ctx->use();
+    dense_gemm_run(ctx, dtype, m, n, k, alpha_re, alpha_im, A, lda, B, ldb, beta_re, beta_im, C, ldc);
   });
 }
 

@@ -1,0 +1,707 @@
+// dense_dev.hip -- dense matrices that live on the device: C = alpha A B + beta C on the gfx950 matrix cores (MFMA), a blocked LU
+// with partial pivoting built around that product, and exponential!(A) for a device matrix on top of both
+// (exp.jl:56-58 -> exponential!(A, ExpMethodHigham2005(false)), exp_noalloc.jl:114-168; test/gpu/gputests.jl:22-39).
+//
+// The algorithm is host_dense.h's expm_higham2005base without gebal / unbalance: opnorm(A, 1) with fp64 column sums, Pade order by
+// the thresholds 0.015 / 0.25 / 0.95 / 2.1, above 2.1 s = max(0, ceil(log2(nA / 5.4))) exact scalings by 1/2 and Pade 13, Horner
+// in A^2 with the coefficients converted to the element type, (V - U) X = (V + U) by LU with partial pivoting, s squarings.
+// s is NOT capped at 8 as in the reference's generated evaluation graphs (they under-scale for nA >= 1382.4): it is unbounded like
+// exp_baseexp.jl and the host routine.
+//
+// Product kernel: one workgroup of 4 waves (2 x 2) per BM x BN tile of C, K in steps of 16 through LDS.  The real planes of a tile
+// are kept in LDS as  As[k][BM + 16]  (rows contiguous, as in the column-major source) and  Bs[col][16 + 2]  (k contiguous, as in
+// the source): both fill passes read global memory along its contiguous direction, and both fragment reads are free of bank
+// conflicts (the 16 rows of a fragment are consecutive words, its k-quads sit 16 words apart mod 32; a B column step is 18 words).
+// Edge tiles are zero-filled in LDS and the stores predicated.  Every element type runs v_mfma_*_16x16x4: A / B fragments are one
+// value per lane (lane l: index l & 15, k = l >> 4).  The kernel computes C' = B' A' (first operand: B fragment, second: A
+// fragment), so the lane index of the accumulator is a ROW of C and a 16-lane group stores 16 consecutive rows of one column.
+// Accumulator register r of lane l is column (l >> 4) * 4 + r of the fragment for f32 and (l >> 4) + 4 r for f64.
+// Complex types: the fill pass splits (re, im) into two LDS planes; four real MFMA per k-step into two accumulators
+// (re: Ar Br - Ai Bi, im: Ar Bi + Ai Br), the minus sign applied to the Ai fragment after it is read.
+#include <chrono>
+#include <cmath>
+
+#include "engine.h"
+
+namespace expv_mi {
+namespace {
+
+// Tile choice of the product kernel: the big tile (128 x 128; ComplexF64: 128 x 64) from this many elements of C on, the small one
+// (64 x 64) below.  Measured (profiles/expm_device.txt): at 1024^2 outputs the small tile is 1.7 - 3 x faster for every type (the
+// big one leaves 3/4 of the CUs idle); at 4096^2 the big tile wins for Float32 (103 vs 88 TFLOP/s) and loses 3 - 9 % for the other
+// three types, which therefore stay on the small tile at every size (BigTile<T>::by_size).
+constexpr int64_t GEMM_BIG_TILE_MIN_OUTPUTS = (int64_t)4096 * 4096;
+
+constexpr int GEMM_THREADS = 256, GEMM_BK = 16, GEMM_LDB = GEMM_BK + 2, GEMM_APAD = 16;
+constexpr int LU_NB = 32;            // panel width of the LU, block size of the triangular solves
+constexpr int PANEL_THREADS = 512, EW_THREADS = 256, TRS_THREADS = 64;
+
+template <class R> struct Mfma;
+template <> struct Mfma<float> {
+  typedef float acc_t __attribute__((ext_vector_type(4)));
+  __device__ static inline acc_t run(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+  __device__ static inline int reg_index(int lane, int r) { return (lane >> 4) * 4 + r; }
+};
+template <> struct Mfma<double> {
+  typedef double acc_t __attribute__((ext_vector_type(4)));
+  __device__ static inline acc_t run(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+  __device__ static inline int reg_index(int lane, int r) { return (lane >> 4) + 4 * r; }      // NOT the f32 map
+};
+
+__device__ inline float re_of(float a) { return a; }
+__device__ inline float im_of(float) { return 0.0f; }
+__device__ inline double re_of(double a) { return a; }
+__device__ inline double im_of(double) { return 0.0; }
+__device__ inline float re_of(cplx32 a) { return a.re; }
+__device__ inline float im_of(cplx32 a) { return a.im; }
+__device__ inline double re_of(cplx a) { return a.re; }
+__device__ inline double im_of(cplx a) { return a.im; }
+template <class T, class R> __device__ inline T make_T(R re, R im);
+template <> __device__ inline float make_T<float, float>(float re, float) { return re; }
+template <> __device__ inline double make_T<double, double>(double re, double) { return re; }
+template <> __device__ inline cplx32 make_T<cplx32, float>(float re, float im) { return make_cplx32(re, im); }
+template <> __device__ inline cplx make_T<cplx, double>(double re, double im) { return make_cplx(re, im); }
+
+// ---------------------------------------------------------------------------------------------- product
+template <class T, int BM, int BN>
+__global__ __launch_bounds__(GEMM_THREADS) void gemm_mfma(int64_t m, int64_t n, int64_t k, T alpha, const T *__restrict__ A, int64_t lda,
+                                                          const T *__restrict__ B, int64_t ldb, T beta, int beta_zero, T *C, int64_t ldc) {
+  using R = typename ST<T>::real_t;
+  using MF = Mfma<R>;
+  using acc_t = typename MF::acc_t;
+  constexpr int NP = ST<T>::nreal;
+  constexpr int LDA_S = BM + GEMM_APAD;
+  constexpr int FM = BM / 32, FN = BN / 32, WM = BM / 2, WN = BN / 2;
+  constexpr int NA = BM * GEMM_BK / GEMM_THREADS, NB = BN * GEMM_BK / GEMM_THREADS;
+  static_assert(BM % 32 == 0 && BN % 32 == 0 && NA >= 1 && NB >= 1, "tile shape");
+  __shared__ R As[NP][GEMM_BK][LDA_S];
+  __shared__ R Bs[NP][BN][GEMM_LDB];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1, l15 = lane & 15, lq = lane >> 4;
+  const int64_t row0 = (int64_t)blockIdx.x * BM, col0 = (int64_t)blockIdx.y * BN;
+
+  acc_t acc[NP][FM][FN];
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) acc[p][i][j] = acc_t{0, 0, 0, 0};
+
+  T ra[NA], rb[NB];
+  auto fetch = [&](int64_t k0) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int e = tid + i * GEMM_THREADS;
+      const int64_t r = row0 + (e % BM), kk = k0 + (e / BM);
+      ra[i] = (r < m && kk < k) ? A[r + kk * lda] : ST<T>::zero();
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int e = tid + i * GEMM_THREADS;
+      const int64_t kk = k0 + (e % GEMM_BK), c = col0 + (e / GEMM_BK);
+      rb[i] = (c < n && kk < k) ? B[kk + c * ldb] : ST<T>::zero();
+    }
+  };
+  fetch(0);
+  for (int64_t k0 = 0; k0 < k; k0 += GEMM_BK) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int e = tid + i * GEMM_THREADS;
+      As[0][e / BM][e % BM] = re_of(ra[i]);
+      if constexpr (NP == 2) As[1][e / BM][e % BM] = im_of(ra[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int e = tid + i * GEMM_THREADS;
+      Bs[0][e / GEMM_BK][e % GEMM_BK] = re_of(rb[i]);
+      if constexpr (NP == 2) Bs[1][e / GEMM_BK][e % GEMM_BK] = im_of(rb[i]);
+    }
+    __syncthreads();
+    if (k0 + GEMM_BK < k) fetch(k0 + GEMM_BK);      // the next tile's loads fly under this tile's MFMA
+#pragma unroll
+    for (int k4 = 0; k4 < GEMM_BK / 4; ++k4) {
+      const int kk = k4 * 4 + lq;
+      R a[NP][FM], b[NP][FN];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+#pragma unroll
+        for (int i = 0; i < FM; ++i) a[p][i] = As[p][kk][wr * WM + i * 16 + l15];
+#pragma unroll
+        for (int j = 0; j < FN; ++j) b[p][j] = Bs[p][wc * WN + j * 16 + l15][kk];
+      }
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          acc[0][i][j] = MF::run(b[0][j], a[0][i], acc[0][i][j]);
+          if constexpr (NP == 2) {
+            acc[0][i][j] = MF::run(b[1][j], -a[1][i], acc[0][i][j]);
+            acc[1][i][j] = MF::run(b[1][j], a[0][i], acc[1][i][j]);
+            acc[1][i][j] = MF::run(b[0][j], a[1][i], acc[1][i][j]);
+          }
+        }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t row = row0 + wr * WM + i * 16 + l15;
+        const int64_t col = col0 + wc * WN + j * 16 + MF::reg_index(lane, r);
+        if (row < m && col < n) {
+          R im = 0;
+          if constexpr (NP == 2) im = acc[1][i][j][r];
+          T v = ST<T>::mul(alpha, make_T<T, R>(acc[0][i][j][r], im));
+          T *dst = C + row + col * ldc;
+          if (!beta_zero) v = ST<T>::add(v, ST<T>::mul(beta, *dst));
+          *dst = v;
+        }
+      }
+}
+
+template <class T> struct BigTile { static constexpr int BM = 128, BN = 128; static constexpr bool by_size = false; };
+template <> struct BigTile<float> { static constexpr int BM = 128, BN = 128; static constexpr bool by_size = true; };
+template <> struct BigTile<cplx> { static constexpr int BM = 128, BN = 64; static constexpr bool by_size = false; };      // two fp64 accumulators per fragment: half the columns
+
+template <class T, class R>
+inline T host_T(R re, R im) {
+  if constexpr (ST<T>::is_complex) { T v; v.re = re; v.im = im; return v; }
+  else return (T)re;
+}
+
+template <class T>
+void gemm_dev(Ctx *ctx, int64_t m, int64_t n, int64_t k, T alpha, const T *A, int64_t lda, const T *B, int64_t ldb, T beta, bool beta_zero,
+              T *C, int64_t ldc) {
+  if (m <= 0 || n <= 0) return;
+  const bool big = ctx->dense_tile == 2 || (ctx->dense_tile != 1 && BigTile<T>::by_size && m * n >= GEMM_BIG_TILE_MIN_OUTPUTS);
+  if (big) {
+    constexpr int BM = BigTile<T>::BM, BN = BigTile<T>::BN;
+    dim3 grid((unsigned)((m + BM - 1) / BM), (unsigned)((n + BN - 1) / BN));
+    gemm_mfma<T, BM, BN><<<grid, GEMM_THREADS, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, beta_zero ? 1 : 0, C, ldc);
+  } else {
+    dim3 grid((unsigned)((m + 63) / 64), (unsigned)((n + 63) / 64));
+    gemm_mfma<T, 64, 64><<<grid, GEMM_THREADS, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, beta_zero ? 1 : 0, C, ldc);
+  }
+  HIPCHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------- element-wise kernels
+// 16 bytes of the real type: the unit of every element-wise pass where the addresses allow it (the rest: a scalar tail)
+template <class R> struct __attribute__((aligned(16))) Pack {
+  static constexpr int N = 16 / (int)sizeof(R);
+  R v[N];
+};
+__device__ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// colsum[j] = sum_i |A[i, j]| in fp64 (one workgroup per column); a non-finite entry makes the sum non-finite
+template <class T>
+__global__ __launch_bounds__(EW_THREADS) void colsum_abs(const T *__restrict__ A, int64_t lda, int64_t n, double *__restrict__ colsum) {
+  using R = typename ST<T>::real_t;
+  constexpr int NP = ST<T>::nreal, N = Pack<R>::N;
+  const R *col = reinterpret_cast<const R *>(A + (int64_t)blockIdx.x * lda);
+  const int64_t len = n * NP;
+  auto mag = [](R re, R im) -> double {
+    if constexpr (NP == 2) return hypot((double)re, (double)im);
+    else return fabs((double)re);
+  };
+  double s = 0.0;
+  int64_t done = 0;
+  if (aligned16(col)) {
+    const int64_t np = len / N;
+    const Pack<R> *pk = reinterpret_cast<const Pack<R> *>(col);
+    for (int64_t i = threadIdx.x; i < np; i += EW_THREADS) {
+      const Pack<R> p = pk[i];
+#pragma unroll
+      for (int q = 0; q < N; q += NP) s += mag(p.v[q], NP == 2 ? p.v[q + NP - 1] : R(0));
+    }
+    done = np * N;
+  }
+  for (int64_t e = done + (int64_t)threadIdx.x * NP; e < len; e += (int64_t)EW_THREADS * NP) s += mag(col[e], NP == 2 ? col[e + NP - 1] : R(0));
+  __shared__ double red[EW_THREADS];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = EW_THREADS / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) colsum[blockIdx.x] = red[0];
+}
+// out[0] = max_j colsum[j], or NaN when one of them is not finite
+__global__ __launch_bounds__(EW_THREADS) void colsum_max(const double *__restrict__ colsum, int64_t n, double *__restrict__ out) {
+  double best = 0.0;
+  int bad = 0;
+  for (int64_t j = threadIdx.x; j < n; j += EW_THREADS) {
+    const double v = colsum[j];
+    if (!(v < INFINITY)) bad = 1;
+    else best = fmax(best, v);
+  }
+  __shared__ double red[EW_THREADS];
+  __shared__ int redbad[EW_THREADS];
+  red[threadIdx.x] = best;
+  redbad[threadIdx.x] = bad;
+  __syncthreads();
+  for (int w = EW_THREADS / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + w]);
+      redbad[threadIdx.x] |= redbad[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = redbad[0] ? (double)NAN : red[0];
+}
+
+// dst[:, j] = scale * src[:, j] for n x n blocks with their own leading dimensions (blockIdx.y = column); scale is a power of two
+template <class T>
+__global__ __launch_bounds__(EW_THREADS) void copy_scale(const T *__restrict__ src, int64_t lds_, T *__restrict__ dst, int64_t ldd, int64_t n,
+                                                         typename ST<T>::real_t scale) {
+  using R = typename ST<T>::real_t;
+  constexpr int N = Pack<R>::N;
+  const R *s = reinterpret_cast<const R *>(src + (int64_t)blockIdx.y * lds_);
+  R *d = reinterpret_cast<R *>(dst + (int64_t)blockIdx.y * ldd);
+  const int64_t len = n * ST<T>::nreal;
+  const int64_t t = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x, nt = (int64_t)gridDim.x * EW_THREADS;
+  int64_t done = 0;
+  if (aligned16(s) && aligned16(d)) {
+    const int64_t np = len / N;
+    for (int64_t i = t; i < np; i += nt) {
+      Pack<R> p = reinterpret_cast<const Pack<R> *>(s)[i];
+#pragma unroll
+      for (int q = 0; q < N; ++q) p.v[q] *= scale;
+      reinterpret_cast<Pack<R> *>(d)[i] = p;
+    }
+    done = np * N;
+  }
+  for (int64_t e = done + t; e < len; e += nt) d[e] = s[e] * scale;
+}
+
+__device__ inline bool is_diag_real_index(int64_t e, int64_t n, int nreal) {      // real word e of a packed n x n matrix: real part of a diagonal entry?
+  if (nreal == 2) {
+    if (e & 1) return false;
+    e >>= 1;
+  }
+  return e % (n + 1) == 0;
+}
+// Horner step on packed matrices seen as `total` real words: U += cu P, V += cv P; the first step (init) starts from U = du I,
+// V = dv I instead of reading them (pade_evaluate: U(i,i) = C[1], V(i,i) = C[0], then the same update)
+template <class R>
+__global__ __launch_bounds__(EW_THREADS) void horner_update(R *__restrict__ U, R *__restrict__ V, const R *__restrict__ P, R cu, R cv, R du, R dv,
+                                                            int init, int64_t total, int64_t n, int nreal) {
+  constexpr int N = Pack<R>::N;
+  const int64_t t = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x, nt = (int64_t)gridDim.x * EW_THREADS;
+  const int64_t np = total / N;
+  for (int64_t i = t; i < np; i += nt) {
+    const Pack<R> p = reinterpret_cast<const Pack<R> *>(P)[i];
+    Pack<R> u, v;
+    if (init) {
+#pragma unroll
+      for (int q = 0; q < N; ++q) {
+        const bool dg = is_diag_real_index(i * N + q, n, nreal);
+        u.v[q] = dg ? du : R(0);
+        v.v[q] = dg ? dv : R(0);
+      }
+    } else {
+      u = reinterpret_cast<const Pack<R> *>(U)[i];
+      v = reinterpret_cast<const Pack<R> *>(V)[i];
+    }
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      u.v[q] += cu * p.v[q];
+      v.v[q] += cv * p.v[q];
+    }
+    reinterpret_cast<Pack<R> *>(U)[i] = u;
+    reinterpret_cast<Pack<R> *>(V)[i] = v;
+  }
+  for (int64_t e = np * N + t; e < total; e += nt) {
+    const bool dg = init && is_diag_real_index(e, n, nreal);
+    const R u0 = init ? (dg ? du : R(0)) : U[e], v0 = init ? (dg ? dv : R(0)) : V[e];
+    U[e] = u0 + cu * P[e];
+    V[e] = v0 + cv * P[e];
+  }
+}
+// in place: (U, V) -> (X, D) = (V + U, V - U)
+template <class R>
+__global__ __launch_bounds__(EW_THREADS) void sum_diff(R *__restrict__ U, R *__restrict__ V, int64_t total) {
+  constexpr int N = Pack<R>::N;
+  const int64_t t = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x, nt = (int64_t)gridDim.x * EW_THREADS;
+  const int64_t np = total / N;
+  for (int64_t i = t; i < np; i += nt) {
+    const Pack<R> u = reinterpret_cast<const Pack<R> *>(U)[i], v = reinterpret_cast<const Pack<R> *>(V)[i];
+    Pack<R> x, d;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      x.v[q] = v.v[q] + u.v[q];
+      d.v[q] = v.v[q] - u.v[q];
+    }
+    reinterpret_cast<Pack<R> *>(U)[i] = x;
+    reinterpret_cast<Pack<R> *>(V)[i] = d;
+  }
+  for (int64_t e = np * N + t; e < total; e += nt) {
+    const R u = U[e], v = V[e];
+    U[e] = v + u;
+    V[e] = v - u;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- the solve
+// pivot weight: |x| for the real types, |re| + |im| for the complex ones (LAPACK's cabs1, what izamax compares)
+template <class T> __device__ inline double pivot_weight(T a) {
+  if constexpr (ST<T>::is_complex) return fabs((double)a.re) + fabs((double)a.im);
+  else return fabs((double)a);
+}
+template <class T> __device__ inline T div_T(T a, T b) {
+  if constexpr (ST<T>::is_complex) {      // Smith's form: no overflow of |b|^2
+    using R = typename ST<T>::real_t;
+    if (fabs((double)b.re) >= fabs((double)b.im)) {
+      const R r = b.im / b.re, d = b.re + b.im * r;
+      return make_T<T, R>((a.re + a.im * r) / d, (a.im - a.re * r) / d);
+    }
+    const R r = b.re / b.im, d = b.re * r + b.im;
+    return make_T<T, R>((a.re * r + a.im) / d, (a.im * r - a.re) / d);
+  } else {
+    return a / b;
+  }
+}
+
+// LU with partial pivoting of the panel D[j0:n, j0:j0+jb] by ONE workgroup (unblocked, right-looking inside the panel).  Row
+// exchanges are applied to the panel's own columns here and recorded in ipiv (absolute rows); stat[0] counts them, stat[1] becomes
+// 1 + column at the first exactly zero pivot column (that column is left as it is, like getrf does).
+// A column step costs two barriers: the pivot candidates of column c + 1 are collected while the rank-1 update of step c writes
+// that column (each thread keeps the first maximal weight of its own ascending rows), reduced inside each wave by lane exchanges
+// and across the waves through a double-buffered LDS slot that every thread reads for itself; the row exchange and the load of
+// the pivot row are one pass.  The first maximal weight wins, as in LAPACK.
+template <class T>
+__global__ __launch_bounds__(PANEL_THREADS) void lu_panel(T *D, int64_t ld, int64_t n, int64_t j0, int jb, int32_t *__restrict__ ipiv,
+                                                          int32_t *__restrict__ stat) {
+  constexpr int NW = PANEL_THREADS / 64;
+  T *P = D + j0 + j0 * ld;
+  const int64_t mrows = n - j0;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ double wbest[2][NW];
+  __shared__ int64_t ibest[2][NW];
+  __shared__ T urow[LU_NB];
+  auto better = [](double x, int64_t xi, double w, int64_t wi) {      // (a NaN weight is taken once and then sticks)
+    return x > w || (x == w && xi < wi) || (x != x && w == w);
+  };
+  int nswap = 0, first_zero = 0;
+  double w = -1.0;
+  int64_t wi = mrows;
+  for (int64_t i = tid; i < mrows; i += PANEL_THREADS) {
+    const double x = pivot_weight(P[i]);
+    if (better(x, i, w, wi)) { w = x; wi = i; }
+  }
+  for (int c = 0; c < jb; ++c) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const double ow = __shfl_xor(w, off);
+      const long long oi = __shfl_xor((long long)wi, off);
+      if (better(ow, (int64_t)oi, w, wi)) { w = ow; wi = (int64_t)oi; }
+    }
+    if (lane == 0) { wbest[c & 1][wave] = w; ibest[c & 1][wave] = wi; }
+    __syncthreads();      // (also: the update of step c - 1 is complete and visible to the whole workgroup)
+    double bw = wbest[c & 1][0];
+    int64_t bi = ibest[c & 1][0];
+#pragma unroll
+    for (int v = 1; v < NW; ++v) {
+      const double ow = wbest[c & 1][v];
+      const int64_t oi = ibest[c & 1][v];
+      if (better(ow, oi, bw, bi)) { bw = ow; bi = oi; }
+    }
+    const bool zero = (bw == 0.0) || bi >= mrows;
+    const int64_t p = zero ? c : bi;
+    if (tid == 0) {
+      ipiv[j0 + c] = (int32_t)(j0 + p);
+      if (p != c) ++nswap;
+      if (zero && first_zero == 0) first_zero = (int)(j0 + c + 1);
+    }
+    if (tid < jb) {      // exchange rows c and p of the panel; the new row c is the pivot row
+      T *q = P + (int64_t)tid * ld;
+      const T vp = q[p];
+      if (p != c) { q[p] = q[c]; q[c] = vp; }
+      urow[tid] = vp;
+    }
+    __syncthreads();
+    w = -1.0;
+    wi = mrows;
+    if (!zero) {
+      const T pivot = urow[c];
+      for (int64_t i = c + 1 + tid; i < mrows; i += PANEL_THREADS) {
+        const T l = div_T(P[i + (int64_t)c * ld], pivot);
+        P[i + (int64_t)c * ld] = l;
+        for (int cc = c + 1; cc < jb; ++cc) {
+          T v = P[i + (int64_t)cc * ld];
+          ST<T>::nfma(v, l, urow[cc]);
+          P[i + (int64_t)cc * ld] = v;
+          if (cc == c + 1) {
+            const double x = pivot_weight(v);
+            if (better(x, i, w, wi)) { w = x; wi = i; }
+          }
+        }
+      }
+    } else if (c + 1 < jb) {      // nothing to eliminate with: the next column's candidates are what is stored
+      for (int64_t i = c + 1 + tid; i < mrows; i += PANEL_THREADS) {
+        const double x = pivot_weight(P[i + (int64_t)(c + 1) * ld]);
+        if (better(x, i, w, wi)) { w = x; wi = i; }
+      }
+    }
+  }
+  if (tid == 0) {
+    stat[0] = stat[0] + nswap;
+    if (first_zero != 0 && stat[1] == 0) stat[1] = first_zero;
+  }
+}
+
+// the panel's row exchanges on columns [0, ncols) of M (one thread per column, the exchanges in order)
+template <class T>
+__global__ __launch_bounds__(EW_THREADS) void apply_row_swaps(T *__restrict__ M, int64_t ld, int64_t ncols, const int32_t *__restrict__ ipiv, int64_t j0,
+                                                              int jb) {
+  const int64_t c = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x;
+  if (c >= ncols) return;
+  T *col = M + c * ld;
+  for (int q = 0; q < jb; ++q) {
+    const int64_t r = j0 + q, p = ipiv[r];
+    if (p != r) {
+      const T t = col[r];
+      col[r] = col[p];
+      col[p] = t;
+    }
+  }
+}
+
+// LU_NB values of one column held in registers (every index an unrolled constant).  The complex types keep two real arrays: an array
+// of (re, im) structs ends up in scratch.
+template <class T, bool CX = ST<T>::is_complex> struct ColRegs;
+template <class T> struct ColRegs<T, false> {
+  T v[LU_NB];
+  __device__ inline T get(int i) const { return v[i]; }
+  __device__ inline void set(int i, T x) { v[i] = x; }
+};
+template <class T> struct ColRegs<T, true> {
+  using R = typename ST<T>::real_t;
+  R re[LU_NB], im[LU_NB];
+  __device__ inline T get(int i) const { return make_T<T, R>(re[i], im[i]); }
+  __device__ inline void set(int i, T x) { re[i] = x.re; im[i] = x.im; }
+};
+
+// B[0:jb, c] <- inv(Tri) B[0:jb, c] for every column c < ncols (one thread per column, the block's rows in registers): Tri is the
+// jb x jb block at `tri`, UNIT lower triangular (UPPER = false: forward substitution, the diagonal is not read) or upper triangular
+// (UPPER = true: back substitution).  Blocks narrower than LU_NB are padded with the identity.
+template <class T, bool UPPER>
+__global__ __launch_bounds__(TRS_THREADS) void tri_solve_block(const T *__restrict__ tri, int64_t ldt, int jb, T *__restrict__ B, int64_t ldb, int64_t ncols) {
+  __shared__ T Ts[LU_NB][LU_NB + 1];
+  for (int e = threadIdx.x; e < LU_NB * LU_NB; e += TRS_THREADS) {
+    const int i = e % LU_NB, j = e / LU_NB;
+    T v = ST<T>::zero();
+    if (i < jb && j < jb) v = tri[i + (int64_t)j * ldt];
+    else if (i == j) v = ST<T>::from_real(1.0);
+    Ts[i][j] = v;
+  }
+  __syncthreads();
+  const int64_t c = (int64_t)blockIdx.x * TRS_THREADS + threadIdx.x;
+  if (c >= ncols) return;
+  T *col = B + c * ldb;
+  ColRegs<T> b;
+#pragma unroll
+  for (int i = 0; i < LU_NB; ++i) b.set(i, (i < jb) ? col[i] : ST<T>::zero());
+  // the step index r stays a run-time value (one copy of the loop body) while the registers are only ever indexed by unrolled
+  // constants: the value the NEXT step eliminates with is caught as it is produced
+  if constexpr (!UPPER) {
+    T br = b.get(0);
+#pragma unroll 1
+    for (int r = 0; r < jb; ++r) {
+      T nxt = br;
+#pragma unroll
+      for (int i = 1; i < LU_NB; ++i)
+        if (i > r) {
+          T bi = b.get(i);
+          ST<T>::nfma(bi, Ts[i][r], br);
+          b.set(i, bi);
+          if (i == r + 1) nxt = bi;
+        }
+      br = nxt;
+    }
+  } else {
+    T br = b.get(LU_NB - 1);      // (rows >= jb: zero right-hand side, unit diagonal -- they pass through)
+#pragma unroll 1
+    for (int r = LU_NB - 1; r >= 0; --r) {
+      br = div_T(br, Ts[r][r]);
+      T nxt = br;
+#pragma unroll
+      for (int i = 0; i < LU_NB; ++i) {
+        if (i == r) {
+          b.set(i, br);
+        } else if (i < r) {
+          T bi = b.get(i);
+          ST<T>::nfma(bi, Ts[i][r], br);
+          b.set(i, bi);
+          if (i == r - 1) nxt = bi;
+        }
+      }
+      br = nxt;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < LU_NB; ++i)
+    if (i < jb) col[i] = b.get(i);
+}
+
+// D X = X for packed n x n D and X (both overwritten): right-looking blocked LU with partial pivoting.  Per panel: factor it (one
+// workgroup), exchange the rows of the columns to its right and of X, block row of U and of L^-1 P X by a unit-lower solve, trailing
+// update of D and of the rows of X below through the product kernel (alpha = -1, beta = 1) -- the forward substitution of the n
+// right-hand sides rides along with the factorisation.  Then back substitution, blocked the same way.
+template <class T>
+void lu_solve_dev(Ctx *ctx, int64_t n, T *D, T *X, int32_t *ipiv, int32_t *stat) {
+  hipStream_t s = ctx->stream;
+  const T one = host_T<T, double>(1.0, 0.0), minus_one = host_T<T, double>(-1.0, 0.0);
+  for (int64_t j0 = 0; j0 < n; j0 += LU_NB) {
+    const int jb = (int)std::min<int64_t>(LU_NB, n - j0);
+    const int64_t right = n - j0 - jb;      // columns right of / rows below the panel
+    lu_panel<T><<<1, PANEL_THREADS, 0, s>>>(D, n, n, j0, jb, ipiv, stat);
+    if (right > 0) apply_row_swaps<T><<<(unsigned)((right + EW_THREADS - 1) / EW_THREADS), EW_THREADS, 0, s>>>(D + (j0 + jb) * n, n, right, ipiv, j0, jb);
+    apply_row_swaps<T><<<(unsigned)((n + EW_THREADS - 1) / EW_THREADS), EW_THREADS, 0, s>>>(X, n, n, ipiv, j0, jb);
+    const T *L11 = D + j0 + j0 * n;
+    if (right > 0)
+      tri_solve_block<T, false><<<(unsigned)((right + TRS_THREADS - 1) / TRS_THREADS), TRS_THREADS, 0, s>>>(L11, n, jb, D + j0 + (j0 + jb) * n, n, right);
+    tri_solve_block<T, false><<<(unsigned)((n + TRS_THREADS - 1) / TRS_THREADS), TRS_THREADS, 0, s>>>(L11, n, jb, X + j0, n, n);
+    HIPCHECK(hipGetLastError());
+    if (right > 0) {
+      const T *L21 = D + (j0 + jb) + j0 * n;
+      gemm_dev<T>(ctx, right, right, jb, minus_one, L21, n, D + j0 + (j0 + jb) * n, n, one, false, D + (j0 + jb) + (j0 + jb) * n, n);
+      gemm_dev<T>(ctx, right, n, jb, minus_one, L21, n, X + j0, n, one, false, X + (j0 + jb), n);
+    }
+  }
+  for (int64_t j0 = ((n - 1) / LU_NB) * LU_NB; j0 >= 0; j0 -= LU_NB) {
+    const int jb = (int)std::min<int64_t>(LU_NB, n - j0);
+    tri_solve_block<T, true><<<(unsigned)((n + TRS_THREADS - 1) / TRS_THREADS), TRS_THREADS, 0, s>>>(D + j0 + j0 * n, n, jb, X + j0, n, n);
+    HIPCHECK(hipGetLastError());
+    if (j0 > 0) gemm_dev<T>(ctx, j0, n, jb, minus_one, D + j0 * n, n, X + j0, n, one, false, X, n);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- exponential!(A)
+// six n x n matrices + pivots + column sums + status words, kept in the context and grown on demand: a loop of calls allocates nothing
+struct DenseWs {
+  DevBuf W[6], colsum, ipiv, stat;
+  void *pin = nullptr;      // pinned host mirror of `stat`
+  ~DenseWs() { if (pin) (void)hipHostFree(pin); }
+};
+struct StatWords {      // device `stat` buffer / its host mirror
+  double norm1;
+  int32_t lu[2];       // row exchanges, 1 + first zero pivot column (0: none)
+};
+
+DenseWs *dense_ws(Ctx *ctx) {
+  DenseWs *ws = reinterpret_cast<DenseWs *>(ctx->ws_dense);
+  if (!ws) {
+    ws = new DenseWs();
+    ctx->ws_dense = ws;
+    ctx->ws_dense_free = [](void *q) { delete reinterpret_cast<DenseWs *>(q); };
+  }
+  return ws;
+}
+
+template <class T>
+void expm_dev(Ctx *ctx, int64_t n, T *A, int64_t lda, int64_t info[8]) {
+  using R = typename ST<T>::real_t;
+  constexpr int NP = ST<T>::nreal;
+  hipStream_t s = ctx->stream;
+  DenseWs *ws = dense_ws(ctx);
+  auto need = [&](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
+  const size_t mat_bytes = ((sizeof(T) * (size_t)n * (size_t)n + 255) / 256) * 256;
+  for (auto &w : ws->W) need(w, mat_bytes);
+  need(ws->colsum, sizeof(double) * (size_t)n);
+  need(ws->ipiv, sizeof(int32_t) * (size_t)n);
+  need(ws->stat, sizeof(StatWords));
+  if (!ws->pin) HIPCHECK(hipHostMalloc(&ws->pin, sizeof(StatWords), hipHostMallocDefault));
+  StatWords *dstat = ws->stat.as<StatWords>(), *hstat = reinterpret_cast<StatWords *>(ws->pin);
+
+  // opnorm(A, 1), column sums in fp64; the norm comes to the host to choose the method, and a non-finite one ends the call here
+  HIPCHECK(hipMemsetAsync(dstat, 0, sizeof(StatWords), s));
+  colsum_abs<T><<<(unsigned)n, EW_THREADS, 0, s>>>(A, lda, n, ws->colsum.as<double>());
+  colsum_max<<<1, EW_THREADS, 0, s>>>(ws->colsum.as<double>(), n, &dstat->norm1);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(hstat, dstat, sizeof(StatWords), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  const double nA = hstat->norm1;
+  if (!std::isfinite(nA)) fail(EXPV_MI_ARGUMENT_ERROR, "ArgumentError: matrix contains Infs or NaNs");
+
+  const double *Cf;
+  int N, si = 0;
+  if (nA <= 2.1) {
+    if (nA > 0.95) { Cf = dense::PADE_C9; N = 10; }
+    else if (nA > 0.25) { Cf = dense::PADE_C7; N = 8; }
+    else if (nA > 0.015) { Cf = dense::PADE_C5; N = 6; }
+    else { Cf = dense::PADE_C3; N = 4; }
+  } else {
+    const double l = std::log2(nA / 5.4);
+    if (l > 0) si = (int)std::ceil(l);
+    Cf = dense::PADE_C13;
+    N = 14;
+  }
+
+  T *As = ws->W[0].as<T>(), *A2 = ws->W[1].as<T>(), *P = ws->W[2].as<T>(), *tmp = ws->W[3].as<T>(), *U = ws->W[4].as<T>(), *V = ws->W[5].as<T>();
+  const T one = host_T<T, double>(1.0, 0.0), zero = host_T<T, double>(0.0, 0.0);
+  const int64_t total = n * n * NP;
+  const unsigned ew_blocks = (unsigned)std::min<int64_t>((total / Pack<R>::N + EW_THREADS) / EW_THREADS, 4096);
+  const dim3 col_grid((unsigned)std::min<int64_t>((n * NP / Pack<R>::N + EW_THREADS) / EW_THREADS, 64), (unsigned)n);
+  auto mm = [&](T *Cm, const T *X, const T *Y) { gemm_dev<T>(ctx, n, n, n, one, X, n, Y, n, zero, true, Cm, n); };
+
+  copy_scale<T><<<col_grid, EW_THREADS, 0, s>>>(A, lda, As, n, n, (R)std::ldexp(1.0, -si));
+  HIPCHECK(hipGetLastError());
+  mm(A2, As, As);
+  const T *Pk = A2;      // A2^k
+  for (int k = 1; k <= N / 2 - 1; ++k) {
+    if (k > 1) {
+      T *dst = (Pk == P) ? tmp : P;
+      mm(dst, Pk, A2);
+      Pk = dst;
+    }
+    horner_update<R><<<ew_blocks, EW_THREADS, 0, s>>>(reinterpret_cast<R *>(U), reinterpret_cast<R *>(V), reinterpret_cast<const R *>(Pk),
+                                                     (R)Cf[2 * k + 1], (R)Cf[2 * k], (R)Cf[1], (R)Cf[0], k == 1 ? 1 : 0, total, n, NP);
+    HIPCHECK(hipGetLastError());
+  }
+  T *X = P, *Y = tmp;      // both free again
+  mm(X, As, U);           // U <- A U
+  sum_diff<R><<<ew_blocks, EW_THREADS, 0, s>>>(reinterpret_cast<R *>(X), reinterpret_cast<R *>(V), total);      // X = V + U, V = V - U
+  HIPCHECK(hipGetLastError());
+  lu_solve_dev<T>(ctx, n, V, X, ws->ipiv.as<int32_t>(), dstat->lu);
+  for (int t = 0; t < si; ++t) {
+    mm(Y, X, X);
+    std::swap(X, Y);
+  }
+  // the exchange count and the zero-pivot flag come back together; nothing has touched the caller's matrix yet
+  HIPCHECK(hipMemcpyAsync(hstat, dstat, sizeof(StatWords), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (hstat->lu[1] != 0) throw dense::SingularError();
+  copy_scale<T><<<col_grid, EW_THREADS, 0, s>>>(X, n, A, lda, n, (R)1);
+  HIPCHECK(hipGetLastError());
+  if (info) {
+    info[0] = N - 1;
+    info[1] = si;
+    info[2] = hstat->lu[0];
+  }
+}
+
+}  // namespace
+
+void dense_gemm_run(Ctx *ctx, int dtype, int64_t m, int64_t n, int64_t k, double alpha_re, double alpha_im, const void *A, int64_t lda,
+                    const void *B, int64_t ldb, double beta_re, double beta_im, void *C, int64_t ldc) {
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    gemm_dev<T>(ctx, m, n, k, host_T<T, double>(alpha_re, alpha_im), reinterpret_cast<const T *>(A), lda, reinterpret_cast<const T *>(B), ldb,
+                host_T<T, double>(beta_re, beta_im), beta_re == 0.0 && beta_im == 0.0, reinterpret_cast<T *>(C), ldc);
+  });
+}
+
+void dense_expm_run(Ctx *ctx, int dtype, int64_t n, void *A_dev, int64_t lda, int64_t info[8]) {
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    expm_dev<T>(ctx, n, reinterpret_cast<T *>(A_dev), lda, info);
+  });
+}
+
+}  // namespace expv_mi

@@ -153,6 +153,9 @@ struct Ctx {
   void *ws_batch = nullptr;   // cached device buffers of expv_batch (owned; see engine_batch.hip)
   size_t ws_batch_bytes = 0;  // ... and how many bytes they hold
   void (*ws_batch_free)(void *) = nullptr;
+  void *ws_dense = nullptr;   // workspace of the dense device exponential: six n x n matrices + pivots (owned; dense_dev.hip)
+  void (*ws_dense_free)(void *) = nullptr;
+  int dense_tile = 0;         // tile of the dense product kernel: 0 by size, 1 small, 2 big (EXPV_MI_DENSE_TILE at creation; A/B of tools/expm_device.py)
   // cumulative counters (expv_mi_ctx_counters): what ran, and whether a bounded device wait ever expired
   int64_t cnt_steps = 0, cnt_fact = 0, cnt_live = 0, cnt_serial_redo = 0, cnt_wave_redo = 0, cnt_opapply = 0, cnt_pipe = 0, cnt_copy = 0;
   int last_path = 0;                      // EXPV_MI_PATH_* flags of the most recent factorisation
@@ -514,6 +517,14 @@ void ks_set_row_order(Ks &ks, const std::shared_ptr<RowPerm> &want);
 void expv_batch_run(Ctx *ctx, int dtype, int64_t n, int nprob, const int32_t *rowptr, const int32_t *colind,
                     const void *vals, int64_t nnz, int mat_loc, const double *t, const void *b, int64_t ldb, int b_loc,
                     void *w, int64_t ldw, int w_loc, const expv_mi_arnoldi_opts &o, int32_t *m_used);
+
+// ---- dense_dev.hip ------------------------------------------------------------------------
+// C = alpha A B + beta C for column-major device blocks on the matrix cores, enqueued on the context's stream (beta == 0: C is not read)
+void dense_gemm_run(Ctx *ctx, int dtype, int64_t m, int64_t n, int64_t k, double alpha_re, double alpha_im, const void *A, int64_t lda,
+                    const void *B, int64_t ldb, double beta_re, double beta_im, void *C, int64_t ldc);
+// exponential!(A) of a device matrix in place (Higham 2005 without balancing); info[0..2] = Pade order, squarings, row exchanges.
+// Synchronises the stream twice (norm; LU status) and leaves the copy into A enqueued.
+void dense_expm_run(Ctx *ctx, int dtype, int64_t n, void *A_dev, int64_t lda, int64_t info[8]);
 
 // ---- engine_drivers.hip --------------------------------------------------------------------
 void phiv_timestep_run(Ctx *ctx, Op &op, int nts, double *ts, const void *B, int64_t ldb, int ncoef, int b_loc,

@@ -280,6 +280,29 @@ int expv_mi_op_apply(expv_mi_op_t op, const void *x, int x_loc, void *y, int y_l
 int expv_mi_gemv_block(expv_mi_ctx_t ctx, int dtype, int64_t nrows, int64_t ncols, const void *A, int64_t lda,
                        const void *x, void *y, void *scratch, int nsplit);
 
+/* exponential!(A) for a dense matrix on the device -- exp.jl:56-58 -> exponential!(A, ExpMethodHigham2005(false)),
+ * exp_noalloc.jl:114-168; test/gpu/gputests.jl:22-39.  A: column-major n x n, leading dimension lda >= n, overwritten with exp(A);
+ * rows n..lda-1 of every column are neither read nor written.  loc = EXPV_MI_DEVICE: a device pointer on the context's device;
+ * EXPV_MI_HOST: staged through HBM, result copied back.  All four element types.  Always computed on the device (no host fallback
+ * at any n): opnorm(A, 1) with fp64 column sums, Pade order 3 / 5 / 7 / 9 / 13 by the thresholds 0.015 / 0.25 / 0.95 / 2.1, above
+ * 2.1 s = max(0, ceil(log2(nA / 5.4))) exact scalings by 1/2, Horner in A^2 (products on the matrix cores), (V - U) X = (V + U) by a
+ * blocked LU with partial pivoting, s squarings.  No balancing, like the reference's GPU dispatch.  ONE deliberate difference: the
+ * reference's generated evaluation graphs stop at 2^-8 (exp_generated/exp_13.jl:19) and under-scale for nA >= 1382.4; here s is
+ * unbounded, like exp_baseexp.jl and expv_mi_host_expm.
+ * A non-finite opnorm(A, 1) answers EXPV_MI_ARGUMENT_ERROR ("ArgumentError: matrix contains Infs or NaNs"), an exactly zero pivot
+ * column of the LU EXPV_MI_SINGULAR; A is untouched in both cases.  n = 0 does nothing.  Complete on return unless the context's
+ * outputs are stream-ordered (expv_mi_ctx_set_async_outputs).
+ * info (may be NULL): [0] Pade order used (3,5,7,9,13), [1] squarings s, [2] row exchanges of the solve's LU, [3] whole call in
+ * microseconds, [4..7] 0. */
+int expv_mi_expm(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t info[8]);
+
+/* mul!(C, A, B, alpha, beta): C = alpha A B + beta C for DEVICE-resident column-major blocks (A m x k, B k x n, C m x n), enqueued on
+ * the context's stream, stream-ordered like expv_mi_gemv_block.  The product kernel of expv_mi_expm (gfx950 matrix cores); C must not
+ * alias A or B.  beta == 0 does not read C.  alpha_im / beta_im must be 0 for the real types.  The tile (64 x 64 or 128 x 128) is
+ * chosen by size; a context created under EXPV_MI_DENSE_TILE=1 / 2 always takes the small / big one (A/B runs, tests). */
+int expv_mi_gemm(expv_mi_ctx_t ctx, int dtype, int64_t m, int64_t n, int64_t k, double alpha_re, double alpha_im,
+                 const void *A, int64_t lda, const void *B, int64_t ldb, double beta_re, double beta_im, void *C, int64_t ldc);
+
 /* ------------------------------------------------------------------ KrylovSubspace --- */
 /* KrylovSubspace{T,U}(n, maxiter, augmented)  (arnoldi.jl:63-76).  V lives in HBM,
  * (n+augmented) x (maxiter+1); H is host-resident, (maxiter+1) x (maxiter + (augmented != 0)),

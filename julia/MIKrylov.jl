@@ -201,6 +201,31 @@ ld(a::MIMatrix) = max(a.dims[1], 1)
 ncols(a::MIVector) = 1
 ncols(a::MIMatrix) = a.dims[2]
 
+# ---- dense matrices in HBM: exponential!(A) for a GPU array (exp.jl:56-58), mul!(C, A, B, alpha, beta) -----------------
+# Computed on the device at every n (matrix-core products + a pivoted blocked LU).  Like the reference's GPU dispatch it runs
+# ExpMethodHigham2005 WITHOUT balancing; unlike the generated evaluation graph it does not cap the scaling at 2^-8.
+function ExponentialUtilities.exponential!(A::MIMatrix{T}) where {T <: MIScalar}
+    n = LinearAlgebra.checksquare(A)
+    info = zeros(Int64, 8)      # Pade order, squarings, row exchanges of the LU, microseconds
+    check(ccall((:expv_mi_expm, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Int64, Cint, Ptr{Int64}),
+                ctx().h, dtype(T), n, A.ptr, ld(A), DEVICE, info), ctx().h)
+    A
+end
+# (do_balancing is ignored, as exp.jl:56-58 ignores it for an AbstractGPUArray)
+ExponentialUtilities.exponential!(A::MIMatrix{T}, ::ExponentialUtilities.ExpMethodHigham2005, cache = nothing) where {T <: MIScalar} =
+    ExponentialUtilities.exponential!(A)
+function LinearAlgebra.mul!(C::MIMatrix{T}, A::MIMatrix{T}, B::MIMatrix{T}, α::Number, β::Number) where {T <: MIScalar}
+    m, n, k = size(C, 1), size(C, 2), size(A, 2)
+    (size(A, 1) == m && size(B, 1) == k && size(B, 2) == n) || throw(DimensionMismatch("mul!: C is $(size(C)), A is $(size(A)), B is $(size(B))"))
+    (T <: Real && !(isreal(α) && isreal(β))) && throw(InexactError(:mul!, T, α))
+    check(ccall((:expv_mi_gemm, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Cdouble, Cdouble, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cdouble, Cdouble, Ptr{Cvoid}, Int64),
+                ctx().h, dtype(T), m, n, k, real(α), imag(α), A.ptr, ld(A), B.ptr, ld(B), real(β), imag(β), C.ptr, ld(C)), ctx().h)
+    sync()
+    C
+end
+LinearAlgebra.mul!(C::MIMatrix{T}, A::MIMatrix{T}, B::MIMatrix{T}) where {T <: MIScalar} = LinearAlgebra.mul!(C, A, B, true, false)
+
 # ---- operator: the contract of docs/src/interfaces.md:7-36 (eltype, size, mul!, ishermitian, opnorm) --------------
 mutable struct MIOperator{T}
     h::Ptr{Cvoid}
