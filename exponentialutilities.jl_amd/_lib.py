@@ -101,6 +101,7 @@ PROTOTYPES = {
     "expv_mi_op_apply": (_i, [_vp, _vp, _i, _vp, _i]),
     "expv_mi_gemv_block": (_i, [_vp, _i, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i]),
     "expv_mi_expm": (_i, [_vp, _i, _i64, _vp, _i64, _i, _vp]),
+    "expv_mi_phi": (_i, [_vp, _i, _i64, _i, _vp, _i64, _vp, _i64, _i, _vp]),
     "expv_mi_gemm": (_i, [_vp, _i, _i64, _i64, _i64, _d, _d, _vp, _i64, _vp, _i64, _d, _d, _vp, _i64]),
     "expv_mi_ks_create": (_i, [_vp, _i, _i, _i64, _i, _i, _pvp]),
     "expv_mi_ks_destroy": (_i, [_vp]),

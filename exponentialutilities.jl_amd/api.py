@@ -30,7 +30,7 @@ __all__ = [
     "Context", "default_context", "MIOperator", "DeviceArray", "KrylovSubspace", "arnoldi", "arnoldi_",
     "lanczos_", "expv", "expv_", "phiv", "phiv_", "expv_timestep", "expv_timestep_", "phiv_timestep",
     "phiv_timestep_", "kiops", "timestep_caches", "expv_batch", "expv_batch_multi", "RcclComm", "rccl_available", "rccl_unique_id", "ExpvMIError", "DimensionMismatch", "host_expm",
-    "exponential", "exponential_", "mul_",
+    "exponential", "exponential_", "mul_", "phi", "phi_",
     "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
 ]
 
@@ -1346,6 +1346,151 @@ def exponential(A, ctx=None, return_info=False):
     else:
         B = np.array(A, order="F", copy=True)
     return exponential_(B, ctx=ctx, return_info=return_info)
+
+
+PHI_MAX_K = 16
+_PHI_INFO = ("degree", "scalings", "products", "microseconds")
+
+
+def _device_view(base, offset, shape):
+    """a DeviceArray over part of another one's storage (the parent is kept alive)"""
+    v = DeviceArray.__new__(DeviceArray)
+    v.ctx, v.shape, v.dtype, v._base = base.ctx, tuple(shape), base.dtype, base
+    v.nbytes = int(np.prod(v.shape)) * v.dtype.itemsize
+    v.ptr = base.ptr + int(offset)
+    return v
+
+
+def _dense_kind(x):
+    return "device" if isinstance(x, DeviceArray) else "torch" if _is_torch(x) else "numpy" if isinstance(x, np.ndarray) else None
+
+
+def _phi_order(k, what):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) <= PHI_MAX_K:
+        raise ValueError(f"{what}: k must be an integer in 0..{PHI_MAX_K}, not {k!r}")
+    return int(k)
+
+
+def _phi_blocks(out, n, k, dt, ka):
+    """`out` of phi! as a list of k + 1 n x n matrices: a sequence of them, or the blocks of one n x (k + 1) n slab"""
+    if isinstance(out, (list, tuple)):
+        blocks = list(out)
+        if len(blocks) != k + 1:
+            raise DimensionMismatch(f"phi!: out has {len(blocks)} matrices, k + 1 = {k + 1}")
+    else:
+        if tuple(out.shape) != (n, (k + 1) * n):
+            raise DimensionMismatch(f"phi!: out is {tuple(out.shape)}, need {k + 1} matrices or one {(n, (k + 1) * n)} slab")
+        if isinstance(out, DeviceArray):
+            blocks = [_device_view(out, j * n * n * out.dtype.itemsize, (n, n)) for j in range(k + 1)]
+        else:
+            blocks = [out[:, j * n:(j + 1) * n] for j in range(k + 1)]
+    for b in blocks:
+        if _dense_kind(b) != ka or (ka == "torch" and not b.is_cuda):
+            raise TypeError("phi!: out and A must be of one kind (numpy arrays, torch GPU tensors or DeviceArrays)")
+        if tuple(b.shape) != (n, n):
+            raise DimensionMismatch(f"phi!: an output matrix is {tuple(b.shape)}, A is {(n, n)}")
+        if _dense_np_dtype(b) != dt:
+            raise TypeError(f"phi!: out must have A's element type {dt}")
+    return blocks
+
+
+def _mat_layout(x, n):
+    """(pointer, leading dimension, "col" / "row") of an n x n numpy array or torch tensor in one of the two plain layouts, else None"""
+    if _is_torch(x):
+        s0, s1, ptr = x.stride(0), x.stride(1), x.data_ptr()
+    else:
+        if x.strides[0] % x.itemsize or x.strides[1] % x.itemsize:
+            return None
+        s0, s1, ptr = x.strides[0] // x.itemsize, x.strides[1] // x.itemsize, x.ctypes.data
+    if n <= 1:
+        return ptr, 1, "any"
+    if s0 == 1 and s1 >= n:
+        return ptr, s1, "col"
+    if s1 == 1 and s0 >= n:
+        return ptr, s0, "row"
+    return None
+
+
+def phi_(out, A, k, ctx=None, return_info=False):
+    """phi!(out, A, k) for a dense matrix, computed on the device (phi.jl:159-257; expv_mi_phi: scaling and recovering with a Taylor
+    core): out[j] <- phi_j(A), j = 0 .. k <= 16, A unchanged.  A: a 2-D torch tensor on the GPU, a DeviceArray or a numpy array
+    (staged through HBM); out: a sequence of k + 1 matrices of A's kind and element type, or one n x (k + 1) n slab whose blocks
+    they are.  Column-major storage is used in place; so is row-major storage when A and every out[j] have it -- phi_j(A') =
+    phi_j(A)' --; mixed or strided layouts go through a copy.  Returns out (and, with return_info, a dict: Taylor degree, scalings,
+    products, microseconds).  A non-finite entry raises ArgumentError and leaves out as it was."""
+    dt = _dense_np_dtype(A)
+    n = _square(tuple(A.shape), "phi!")
+    k = _phi_order(k, "phi!")
+    ka = _dense_kind(A)
+    if ka is None:
+        raise TypeError("phi!: pass a numpy array, a torch GPU tensor or a DeviceArray")
+    if ka == "torch" and not A.is_cuda:
+        raise TypeError("torch tensors must live on the GPU (or pass a numpy array)")
+    blocks = _phi_blocks(out, n, k, dt, ka)
+    info = (C.c_int64 * 8)()
+
+    def run(c, a_ptr, lda, ptrs, ldo, loc):
+        arr = (C.c_void_p * (k + 1))(*[int(p) for p in ptrs])
+        _check(L.load().expv_mi_phi(c._h, _code(dt), n, k, a_ptr, max(int(lda), n, 1), arr, max(int(ldo), n, 1), loc, info), c._h)
+
+    if n > 0:
+        if ka == "device":
+            run(ctx or A.ctx, A.ptr, n, [b.ptr for b in blocks], n, L.DEVICE)
+        else:
+            is_t = ka == "torch"
+            c = ctx or default_context()
+            loc = L.DEVICE if is_t else L.HOST
+            if not is_t and not all(b.flags.writeable for b in blocks):
+                raise ValueError("phi!: an output array is read-only")
+            lay = [_mat_layout(x, n) for x in [A] + blocks]
+            orient = {l[2] for l in lay if l is not None} - {"any"}
+            if all(l is not None for l in lay) and len(orient) <= 1 and len({l[1] for l in lay[1:]}) == 1:
+                if is_t:
+                    _torch_ready(A, *blocks)
+                run(c, lay[0][0], lay[0][1], [l[0] for l in lay[1:]], lay[1][1], loc)
+            elif is_t:          # row-major copies: the transposed problem, column-major
+                import torch
+                a = A.contiguous()
+                tmp = torch.empty((k + 1, n, n), dtype=A.dtype, device=A.device)
+                _torch_ready(a, tmp)
+                run(c, a.data_ptr(), n, [tmp[j].data_ptr() for j in range(k + 1)], n, loc)
+                for j, b in enumerate(blocks):
+                    b.copy_(tmp[j])
+            else:
+                a = np.asfortranarray(A)
+                tmp = np.empty((n, (k + 1) * n), dtype=dt, order="F")
+                run(c, a.ctypes.data, n, [tmp.ctypes.data + j * n * n * dt.itemsize for j in range(k + 1)], n, loc)
+                for j, b in enumerate(blocks):
+                    b[...] = tmp[:, j * n:(j + 1) * n]
+    if return_info:
+        return out, dict(zip(_PHI_INFO, (int(v) for v in info[:4])))
+    return out
+
+
+def phi(A, k, ctx=None, return_info=False):
+    """phi(A, k): [phi_0(A), ..., phi_k(A)] as the block views of one new n x (k + 1) n slab of A's kind (see phi_)."""
+    dt = _dense_np_dtype(A)
+    n = _square(tuple(A.shape), "phi")
+    k = _phi_order(k, "phi")
+    if isinstance(A, DeviceArray):
+        slab = DeviceArray((n, (k + 1) * n), dt, ctx or A.ctx)
+        blocks = [_device_view(slab, j * n * n * dt.itemsize, (n, n)) for j in range(k + 1)]
+    elif _is_torch(A):
+        import torch
+        if not A.is_cuda:
+            raise TypeError("torch tensors must live on the GPU (or pass a numpy array)")
+        if n > 1 and A.stride(0) == 1:        # column-major A: a column-major slab
+            slab = torch.empty(((k + 1) * n, n), dtype=A.dtype, device=A.device).t()
+        else:
+            slab = torch.empty((n, (k + 1) * n), dtype=A.dtype, device=A.device)
+        blocks = [slab[:, j * n:(j + 1) * n] for j in range(k + 1)]
+    else:
+        if not isinstance(A, np.ndarray):
+            raise TypeError("phi: pass a numpy array, a torch GPU tensor or a DeviceArray")
+        slab = np.empty((n, (k + 1) * n), dtype=dt, order="C" if (n > 1 and A.flags.c_contiguous) else "F")
+        blocks = [slab[:, j * n:(j + 1) * n] for j in range(k + 1)]
+    res = phi_(blocks, A, k, ctx=ctx, return_info=return_info)
+    return (blocks, res[1]) if return_info else blocks
 
 
 def _dense_dev_arg(x, dt, what):

@@ -1988,6 +1988,56 @@ int expv_mi_expm(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, 
   });
 }
 
+int expv_mi_phi(expv_mi_ctx_t ctx, int dtype, int64_t n, int k, const void *A, int64_t lda, void *const *out, int64_t ldo, int loc,
+                int64_t info[8]) {
+  return guarded(ctx, [&] {
+    const auto t0 = std::chrono::steady_clock::now();
+    check_device_dtype(dtype, "phi");
+    if (loc != EXPV_MI_HOST && loc != EXPV_MI_DEVICE) fail(EXPV_MI_ARGUMENT_ERROR, "phi: unknown loc");
+    if (n < 0 || lda < n || ldo < n) fail(EXPV_MI_ARGUMENT_ERROR, "phi: bad n / lda / ldo");
+    if (k < 0 || k > dense_phi_max_k()) fail(EXPV_MI_ARGUMENT_ERROR, "phi: k outside 0..16");
+    if (info) std::fill(info, info + 8, (int64_t)0);
+    if (n == 0) return;
+    if (!A || !out) fail(EXPV_MI_ARGUMENT_ERROR, "phi: null pointer");
+    const size_t esz = dtype_size(dtype);
+    // no out[j] may share a byte with A or with another out[i].  The spans decide the usual case; where they intersect (the blocks of
+    // a row-major slab interleave) every column of one matrix is compared with the at most two columns of the other it can reach
+    const int64_t W = n * (int64_t)esz;
+    auto meet = [&](const void *pp, int64_t ldp, const void *qq, int64_t ldq) {
+      const int64_t p = (int64_t)reinterpret_cast<uintptr_t>(pp), q = (int64_t)reinterpret_cast<uintptr_t>(qq);
+      const int64_t Lp = ldp * (int64_t)esz, Lq = ldq * (int64_t)esz;
+      if (p + (n - 1) * Lp + W <= q || q + (n - 1) * Lq + W <= p) return false;
+      for (int64_t c = 0; c < n; ++c) {
+        const int64_t x = q + c * Lq - p;      // column c of q covers [x, x + W) relative to p
+        if (x + W <= 0) continue;
+        const int64_t c1 = std::max<int64_t>(0, x) / Lp;
+        for (int64_t d = c1; d <= c1 + 1 && d < n; ++d)
+          if (d * Lp < x + W && x < d * Lp + W) return true;
+      }
+      return false;
+    };
+    for (int j = 0; j <= k; ++j) {
+      if (!out[j]) fail(EXPV_MI_ARGUMENT_ERROR, "phi: null pointer");
+      if (meet(A, lda, out[j], ldo)) fail(EXPV_MI_ARGUMENT_ERROR, "phi: an output overlaps A");
+      for (int i = 0; i < j; ++i)
+        if (meet(out[i], ldo, out[j], ldo)) fail(EXPV_MI_ARGUMENT_ERROR, "phi: two outputs overlap");
+    }
+    if (!ctx) fail(EXPV_MI_ARGUMENT_ERROR, "phi: null context");
+    if (n > 65535) fail(EXPV_MI_UNSUPPORTED, "phi: n > 65535");      // ((k + 1) n <= 65535 * 64 follows: dense_dev.hip)
+    ctx->use();
+    DevBuf stage;
+    int64_t ldd = lda;
+    const void *Ad = stage_in_2d(ctx, A, loc, n, n, lda, esz, stage, &ldd);
+    const char *slab = reinterpret_cast<const char *>(dense_phi_run(ctx, dtype, n, k, Ad, ldd, loc == EXPV_MI_DEVICE ? out : nullptr, ldo, info));
+    if (loc == EXPV_MI_HOST) {
+      for (int j = 0; j <= k; ++j) copy_out_2d(ctx, out[j], loc, ldo, slab + (size_t)j * (size_t)n * (size_t)n * esz, n, n, n, esz);
+    } else if (!ctx->async_out) {
+      HIPCHECK(hipStreamSynchronize(ctx->stream));
+    }
+    if (info) info[3] = (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+  });
+}
+
 int expv_mi_gemm(expv_mi_ctx_t ctx, int dtype, int64_t m, int64_t n, int64_t k, double alpha_re, double alpha_im, const void *A, int64_t lda,
                  const void *B, int64_t ldb, double beta_re, double beta_im, void *C, int64_t ldc) {
   return guarded(ctx, [&] {

@@ -586,6 +586,7 @@ void lu_solve_dev(Ctx *ctx, int64_t n, T *D, T *X, int32_t *ipiv, int32_t *stat)
 // six n x n matrices + pivots + column sums + status words, kept in the context and grown on demand: a loop of calls allocates nothing
 struct DenseWs {
   DevBuf W[6], colsum, ipiv, stat;
+  DevBuf phiS, phiT;        // phi!(out, A, k): the slabs [Phi_0 ... Phi_k] and Phi_0 [Phi_0 ... Phi_k]
   void *pin = nullptr;      // pinned host mirror of `stat`
   ~DenseWs() { if (pin) (void)hipHostFree(pin); }
 };
@@ -686,7 +687,248 @@ void expm_dev(Ctx *ctx, int64_t n, T *A, int64_t lda, int64_t info[8]) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- phi!(out, A, k)
+// phi_0(A) ... phi_k(A) of a device matrix (phi.jl:159-257) by scaling and recovering: s = smallest integer with |A|_1 2^-s <= 1,
+// phi_k(As) by its Taylor series to degree M (Paterson-Stockmeyer, tau = 4), phi_j(As) = As phi_{j+1}(As) + I / j! downwards, then s
+// times phi_0(2X) = phi_0(X)^2, phi_j(2X) = 2^-j (phi_0(X) phi_j(X) + sum_{i=1..j} phi_i(X) / (j - i)!).  DESIGN.md 4.1.2 derives
+// M (18 for the 64-bit types, 10 for the 32-bit ones: the remainder at |As|_1 <= 1 is below the unit roundoff for every k) and
+// counts the products: tau - 1 = 3 powers, M / tau Horner steps (4 or 2), k for the recurrence, one WIDE product per recovery step.
+constexpr int PHI_MAX_K = 16;
+constexpr int PHI_TAU = 4;
+static_assert((int64_t)(PHI_MAX_K + 1) * 65535 <= (int64_t)65535 * 64, "grid.y of the wide product: (k + 1) n / 64 at the largest n");
+
+template <class R> struct PhiTab {      // kernel argument of phi_recover: 1 / d! and 2^-j
+  R inv_fact[PHI_MAX_K + 1], half_pow[PHI_MAX_K + 1];
+};
+template <class R> struct One {         // the scalar twin of Pack<R>
+  static constexpr int N = 1;
+  R v[1];
+};
+
+// One recovery step at position i (in units of W) of every block: S_j <- 2^-j (T_j + sum_{i=1..j} S_i / (j - i)!), T = Phi_0 S.
+// The old Phi_1 .. Phi_k of the position are held in registers (indices are unrolled constants, j <= k is uniform), then the
+// blocks 0 .. k are stored over them.
+template <class R, int KM, class W>
+__device__ inline void phi_recover_at(R *S, const R *T, int64_t block_words, int64_t i, int k, const PhiTab<R> &tab) {
+  W old[KM];
+#pragma unroll
+  for (int j = 1; j <= KM; ++j)
+    if (j <= k) old[j - 1] = reinterpret_cast<const W *>(S + j * block_words)[i];
+#pragma unroll
+  for (int j = 0; j <= KM; ++j)
+    if (j <= k) {
+      W acc = reinterpret_cast<const W *>(T + j * block_words)[i];
+#pragma unroll
+      for (int l = 1; l <= j; ++l)
+#pragma unroll
+        for (int q = 0; q < W::N; ++q) acc.v[q] += old[l - 1].v[q] * tab.inv_fact[j - l];
+#pragma unroll
+      for (int q = 0; q < W::N; ++q) acc.v[q] *= tab.half_pow[j];
+      reinterpret_cast<W *>(S + j * block_words)[i] = acc;
+    }
+}
+// S and T: slabs of k + 1 packed n x n blocks, seen as block_words real words each.  vec: every block starts on a 16-byte boundary
+// (block_words is a multiple of the pack); otherwise the whole pass is scalar.  KM: the compiled register budget, k <= KM.
+template <class R, int KM>
+__global__ __launch_bounds__(EW_THREADS) void phi_recover(R *S, const R *__restrict__ T, int64_t block_words, int k, PhiTab<R> tab, int vec) {
+  const int64_t t = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x, nt = (int64_t)gridDim.x * EW_THREADS;
+  if (vec) {
+    const int64_t np = block_words / Pack<R>::N;
+    for (int64_t i = t; i < np; i += nt) phi_recover_at<R, KM, Pack<R>>(S, T, block_words, i, k, tab);
+  } else {
+    for (int64_t i = t; i < block_words; i += nt) phi_recover_at<R, KM, One<R>>(S, T, block_words, i, k, tab);
+  }
+}
+
+// Paterson-Stockmeyer block on packed n x n matrices seen as `total` real words: B = c0 I + c1 P1 + c2 P2 + c3 P3 (terms l >= nl
+// are not read).  B is the buffer the next Horner product accumulates into (beta = 1).
+template <class R>
+__global__ __launch_bounds__(EW_THREADS) void ps_block(R *__restrict__ B, const R *__restrict__ P1, const R *__restrict__ P2, const R *__restrict__ P3,
+                                                       R c0, R c1, R c2, R c3, int nl, int64_t total, int64_t n, int nreal, int vec) {
+  constexpr int N = Pack<R>::N;
+  const int64_t t = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x, nt = (int64_t)gridDim.x * EW_THREADS;
+  const int64_t np = vec ? total / N : 0;
+  for (int64_t i = t; i < np; i += nt) {
+    Pack<R> b;
+#pragma unroll
+    for (int q = 0; q < N; ++q) b.v[q] = is_diag_real_index(i * N + q, n, nreal) ? c0 : R(0);
+    if (nl > 1) {
+      const Pack<R> p = reinterpret_cast<const Pack<R> *>(P1)[i];
+#pragma unroll
+      for (int q = 0; q < N; ++q) b.v[q] += c1 * p.v[q];
+    }
+    if (nl > 2) {
+      const Pack<R> p = reinterpret_cast<const Pack<R> *>(P2)[i];
+#pragma unroll
+      for (int q = 0; q < N; ++q) b.v[q] += c2 * p.v[q];
+    }
+    if (nl > 3) {
+      const Pack<R> p = reinterpret_cast<const Pack<R> *>(P3)[i];
+#pragma unroll
+      for (int q = 0; q < N; ++q) b.v[q] += c3 * p.v[q];
+    }
+    reinterpret_cast<Pack<R> *>(B)[i] = b;
+  }
+  for (int64_t e = np * N + t; e < total; e += nt) {
+    R b = is_diag_real_index(e, n, nreal) ? c0 : R(0);
+    if (nl > 1) b += c1 * P1[e];
+    if (nl > 2) b += c2 * P2[e];
+    if (nl > 3) b += c3 * P3[e];
+    B[e] = b;
+  }
+}
+
+// M[i, i] += d for a packed n x n matrix (the real part, for the complex types)
+template <class R>
+__global__ __launch_bounds__(EW_THREADS) void add_diag(R *__restrict__ M, int64_t n, int nreal, R d) {
+  const int64_t i = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x;
+  if (i < n) M[i * (n + 1) * nreal] += d;
+}
+
+template <class R, int KM>
+void phi_recover_launch(hipStream_t s, unsigned blocks, R *S, const R *T, int64_t block_words, int k, const PhiTab<R> &tab, int vec) {
+  phi_recover<R, KM><<<blocks, EW_THREADS, 0, s>>>(S, T, block_words, k, tab, vec);
+}
+
+// opnorm(A, 1) with fp64 column sums, brought to the host (one stream synchronisation); NaN when an entry is not finite
+template <class T>
+double norm1_to_host(Ctx *ctx, DenseWs *ws, const T *A, int64_t lda, int64_t n) {
+  hipStream_t s = ctx->stream;
+  auto need = [&](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
+  need(ws->colsum, sizeof(double) * (size_t)n);
+  need(ws->stat, sizeof(StatWords));
+  if (!ws->pin) HIPCHECK(hipHostMalloc(&ws->pin, sizeof(StatWords), hipHostMallocDefault));
+  StatWords *dstat = ws->stat.as<StatWords>(), *hstat = reinterpret_cast<StatWords *>(ws->pin);
+  HIPCHECK(hipMemsetAsync(dstat, 0, sizeof(StatWords), s));
+  colsum_abs<T><<<(unsigned)n, EW_THREADS, 0, s>>>(A, lda, n, ws->colsum.as<double>());
+  colsum_max<<<1, EW_THREADS, 0, s>>>(ws->colsum.as<double>(), n, &dstat->norm1);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(hstat, dstat, sizeof(StatWords), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return hstat->norm1;
+}
+
+// The slab [Phi_0 ... Phi_k] (packed n x n blocks) in the context's workspace; A is only read.  With `out` the blocks are copied to
+// out[j] (device, leading dimension ldo) by kernels on the stream; the call itself synchronises once (the norm).
+template <class T>
+const T *phi_dev(Ctx *ctx, int64_t n, int k, const T *A, int64_t lda, void *const *out, int64_t ldo, int64_t info[8]) {
+  using R = typename ST<T>::real_t;
+  constexpr int NP = ST<T>::nreal, N = Pack<R>::N;
+  hipStream_t s = ctx->stream;
+  DenseWs *ws = dense_ws(ctx);
+  auto need = [&](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
+  const size_t mat_bytes = ((sizeof(T) * (size_t)n * (size_t)n + 255) / 256) * 256;
+  const size_t slab_bytes = ((sizeof(T) * (size_t)n * (size_t)n * (size_t)(k + 1) + 255) / 256) * 256;
+  for (auto &w : ws->W) need(w, mat_bytes);
+  need(ws->phiS, slab_bytes);
+  need(ws->phiT, slab_bytes);
+
+  const double nA = norm1_to_host<T>(ctx, ws, A, lda, n);
+  if (!std::isfinite(nA)) fail(EXPV_MI_ARGUMENT_ERROR, "ArgumentError: matrix contains Infs or NaNs");
+  int si = 0;      // the smallest s with nA 2^-s <= theta = 1, from the exponent (no rounding of a logarithm at the thresholds)
+  if (nA > 1.0) {
+    const double f = std::frexp(nA, &si);      // nA = f 2^si, 0.5 <= f < 1
+    if (f == 0.5) --si;
+  }
+  const int M = sizeof(R) == 8 ? 18 : 10;
+  R c[20];      // c[i] = 1 / (i + k)!, i <= M, in fp64, rounded once
+  PhiTab<R> tab;
+  {
+    double f = 1.0;          // d!
+    for (int d = 0; d <= PHI_MAX_K; ++d) {
+      if (d > 0) f *= d;
+      tab.inv_fact[d] = (R)(1.0 / f);
+      tab.half_pow[d] = (R)std::ldexp(1.0, -d);
+    }
+    f = 1.0;
+    for (int d = 1; d <= k; ++d) f *= d;
+    for (int i = 0; i <= M; ++i) {
+      if (i > 0) f *= (i + k);
+      c[i] = (R)(1.0 / f);
+    }
+  }
+
+  T *As = ws->W[0].as<T>(), *P2 = ws->W[1].as<T>(), *P3 = ws->W[2].as<T>(), *P4 = ws->W[3].as<T>(), *X = ws->W[4].as<T>(), *Y = ws->W[5].as<T>();
+  T *S = ws->phiS.as<T>(), *Tm = ws->phiT.as<T>();
+  const T one = host_T<T, double>(1.0, 0.0), zero = host_T<T, double>(0.0, 0.0);
+  const int64_t nn = n * n, total = nn * NP;
+  const unsigned ew_blocks = (unsigned)std::min<int64_t>((total / N + EW_THREADS) / EW_THREADS, 4096);
+  const dim3 col_grid((unsigned)std::min<int64_t>((n * NP / N + EW_THREADS) / EW_THREADS, 64), (unsigned)n);
+  int products = 0;
+  auto mm = [&](T *Cm, const T *L, const T *Rt, int64_t ncols, bool accumulate) {
+    gemm_dev<T>(ctx, n, ncols, n, one, L, n, Rt, n, accumulate ? one : zero, !accumulate, Cm, n);
+    ++products;
+  };
+  auto is16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+
+  copy_scale<T><<<col_grid, EW_THREADS, 0, s>>>(A, lda, As, n, n, (R)std::ldexp(1.0, -si));
+  HIPCHECK(hipGetLastError());
+  mm(P2, As, As, n, false);
+  mm(P3, P2, As, n, false);
+  mm(P4, P2, P2, n, false);
+  // Horner in As^4 from the top block down; the last step lands in block k of the slab
+  T *Sk = S + (int64_t)k * nn;
+  const int top = M / PHI_TAU;
+  const T *cur = nullptr;
+  for (int b = top; b >= 0; --b) {
+    T *dst = (b == 0) ? Sk : (cur == X ? Y : X);
+    const int nl = std::min(PHI_TAU, M + 1 - b * PHI_TAU);
+    const R *cb = c + b * PHI_TAU;
+    ps_block<R><<<ew_blocks, EW_THREADS, 0, s>>>(reinterpret_cast<R *>(dst), reinterpret_cast<const R *>(As), reinterpret_cast<const R *>(P2),
+                                                reinterpret_cast<const R *>(P3), cb[0], nl > 1 ? cb[1] : R(0), nl > 2 ? cb[2] : R(0),
+                                                nl > 3 ? cb[3] : R(0), nl, total, n, NP, is16(dst) ? 1 : 0);
+    HIPCHECK(hipGetLastError());
+    if (cur) mm(dst, cur, P4, n, true);
+    cur = dst;
+  }
+  // phi_j = As phi_{j+1} + I / j!: the product, then n diagonal entries (a C prefilled with I / j! and beta = 1 would write and
+  // read n^2 entries more per step for the same two launches)
+  for (int j = k - 1; j >= 0; --j) {
+    T *Sj = S + (int64_t)j * nn;
+    mm(Sj, As, Sj + nn, n, false);
+    add_diag<R><<<(unsigned)((n + EW_THREADS - 1) / EW_THREADS), EW_THREADS, 0, s>>>(reinterpret_cast<R *>(Sj), n, NP, tab.inv_fact[j]);
+    HIPCHECK(hipGetLastError());
+  }
+  // recovery: one wide product T = Phi_0 [Phi_0 ... Phi_k], one element-wise pass over both slabs
+  const int vec = (total % N == 0) ? 1 : 0;
+  const unsigned rec_blocks = (unsigned)std::min<int64_t>(((vec ? total / N : total) + EW_THREADS - 1) / EW_THREADS, 8192);
+  for (int t = 0; t < si; ++t) {
+    mm(Tm, S, S, (int64_t)(k + 1) * n, false);
+    ProfScope ps(ctx, EXPV_MI_K_LINCOMB);      // (expv_mi_prof_get: the recovery pass is timed under "lincomb", tools/phi_device.py)
+    R *Sr = reinterpret_cast<R *>(S);
+    const R *Tr = reinterpret_cast<const R *>(Tm);
+    if (k <= 1) phi_recover_launch<R, 1>(s, rec_blocks, Sr, Tr, total, k, tab, vec);
+    else if (k <= 2) phi_recover_launch<R, 2>(s, rec_blocks, Sr, Tr, total, k, tab, vec);
+    else if (k <= 4) phi_recover_launch<R, 4>(s, rec_blocks, Sr, Tr, total, k, tab, vec);
+    else if (k <= 8) phi_recover_launch<R, 8>(s, rec_blocks, Sr, Tr, total, k, tab, vec);
+    else phi_recover_launch<R, PHI_MAX_K>(s, rec_blocks, Sr, Tr, total, k, tab, vec);
+    HIPCHECK(hipGetLastError());
+  }
+  if (out) {
+    for (int j = 0; j <= k; ++j) copy_scale<T><<<col_grid, EW_THREADS, 0, s>>>(S + (int64_t)j * nn, n, reinterpret_cast<T *>(out[j]), ldo, n, (R)1);
+    HIPCHECK(hipGetLastError());
+  }
+  if (info) {
+    info[0] = M;
+    info[1] = si;
+    info[2] = products;
+  }
+  return S;
+}
+
 }  // namespace
+
+int dense_phi_max_k() { return PHI_MAX_K; }
+
+const void *dense_phi_run(Ctx *ctx, int dtype, int64_t n, int k, const void *A_dev, int64_t lda, void *const *out_dev, int64_t ldo,
+                          int64_t info[8]) {
+  const void *slab = nullptr;
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    slab = phi_dev<T>(ctx, n, k, reinterpret_cast<const T *>(A_dev), lda, out_dev, ldo, info);
+  });
+  return slab;
+}
 
 void dense_gemm_run(Ctx *ctx, int dtype, int64_t m, int64_t n, int64_t k, double alpha_re, double alpha_im, const void *A, int64_t lda,
                     const void *B, int64_t ldb, double beta_re, double beta_im, void *C, int64_t ldc) {

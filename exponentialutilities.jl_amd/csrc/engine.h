@@ -525,6 +525,12 @@ void dense_gemm_run(Ctx *ctx, int dtype, int64_t m, int64_t n, int64_t k, double
 // exponential!(A) of a device matrix in place (Higham 2005 without balancing); info[0..2] = Pade order, squarings, row exchanges.
 // Synchronises the stream twice (norm; LU status) and leaves the copy into A enqueued.
 void dense_expm_run(Ctx *ctx, int dtype, int64_t n, void *A_dev, int64_t lda, int64_t info[8]);
+// phi!(out, A, k) of a device matrix (scaling and recovering, Taylor core): returns the slab [Phi_0 ... Phi_k] of packed n x n blocks in
+// the context's workspace and, with out_dev, enqueues the copies to out_dev[j] (leading dimension ldo).  A is only read.
+// info[0..2] = Taylor degree, scalings, products launched.  Synchronises the stream once (norm).
+const void *dense_phi_run(Ctx *ctx, int dtype, int64_t n, int k, const void *A_dev, int64_t lda, void *const *out_dev, int64_t ldo,
+                          int64_t info[8]);
+int dense_phi_max_k();
 
 // ---- engine_drivers.hip --------------------------------------------------------------------
 void phiv_timestep_run(Ctx *ctx, Op &op, int nts, double *ts, const void *B, int64_t ldb, int ncoef, int b_loc,

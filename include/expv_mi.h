@@ -296,6 +296,27 @@ int expv_mi_gemv_block(expv_mi_ctx_t ctx, int dtype, int64_t nrows, int64_t ncol
  * microseconds, [4..7] 0. */
 int expv_mi_expm(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t info[8]);
 
+/* phi!(out, A, k) for a dense matrix on the device -- phi.jl:159-257: out[j] <- phi_j(A), j = 0 .. k (phi_0 = exp).  A: column-major
+ * n x n, leading dimension lda >= n, NOT modified; out: a HOST array of k + 1 pointers to column-major n x n matrices with leading
+ * dimension ldo >= n.  loc applies to A and to every out[j] (EXPV_MI_DEVICE: device pointers; EXPV_MI_HOST: staged through HBM).  Rows
+ * n..ld-1 of every column are neither read nor written.  All four element types, always on the device.
+ * Scaling and recovering: opnorm(A, 1) with fp64 column sums, s = the smallest integer with opnorm 2^-s <= 1 (not capped),
+ * phi_k(A 2^-s) by its Taylor series to degree 18 (64-bit types) / 10 (32-bit types) in Paterson-Stockmeyer form,
+ * phi_j = A 2^-s phi_{j+1} + I / j! downwards, then s times phi_0(2X) = phi_0(X)^2,
+ * phi_j(2X) = 2^-j (phi_0(X) phi_j(X) + sum_{i=1..j} phi_i(X) / (j - i)!), every product on the matrix cores.
+ * The deliberate difference: ONE Taylor core with the fixed threshold 1 for all four element types, where the reference takes a
+ * tabulated Pade approximant for Float64 / ComplexF64 (phi_almohy.jl) and the basis-vector route (k + 1 augmented exponentials) for
+ * the others.  k = 0 computes exp(A) by this path, not by expv_mi_expm's Pade.
+ * There is no NaN-fill convention: a non-finite opnorm(A, 1) answers EXPV_MI_ARGUMENT_ERROR ("ArgumentError: matrix contains Infs or
+ * NaNs").  k < 0, k > 16, an out[j] that overlaps A or another out[i]: EXPV_MI_ARGUMENT_ERROR; n > 65535: EXPV_MI_UNSUPPORTED.  The
+ * results are built in the context's workspace and copied out last: every failure leaves `out` untouched.  Overflow inside the
+ * recovery gives Inf / NaN entries, returned as computed.  n = 0 does nothing.  Complete on return unless the context's outputs are
+ * stream-ordered (expv_mi_ctx_set_async_outputs).
+ * info (may be NULL): [0] Taylor degree, [1] scalings s, [2] matrix products launched (a recovery step's wide product counts once),
+ * [3] whole call in microseconds, [4..7] 0. */
+int expv_mi_phi(expv_mi_ctx_t ctx, int dtype, int64_t n, int k, const void *A, int64_t lda, void *const *out, int64_t ldo, int loc,
+                int64_t info[8]);
+
 /* mul!(C, A, B, alpha, beta): C = alpha A B + beta C for DEVICE-resident column-major blocks (A m x k, B k x n, C m x n), enqueued on
  * the context's stream, stream-ordered like expv_mi_gemv_block.  The product kernel of expv_mi_expm (gfx950 matrix cores); C must not
  * alias A or B.  beta == 0 does not read C.  alpha_im / beta_im must be 0 for the real types.  The tile (64 x 64 or 128 x 128) is

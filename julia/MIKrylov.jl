@@ -226,6 +226,24 @@ function LinearAlgebra.mul!(C::MIMatrix{T}, A::MIMatrix{T}, B::MIMatrix{T}, α::
 end
 LinearAlgebra.mul!(C::MIMatrix{T}, A::MIMatrix{T}, B::MIMatrix{T}) where {T <: MIScalar} = LinearAlgebra.mul!(C, A, B, true, false)
 
+# phi!(out, A, k) (phi.jl:159-257): out[j + 1] <- phi_j(A), A unchanged.  Scaling and recovering with ONE Taylor core for all four
+# element types (the reference: tabulated Pade for Float64 / ComplexF64, the basis-vector route for the others); `caches` and
+# `expmethod` are accepted and ignored -- the workspace lives in the context.  A non-finite entry throws ArgumentError.
+function ExponentialUtilities.phi!(out::Vector{<:MIMatrix{T}}, A::MIMatrix{T}, k::Integer; caches = nothing, expmethod = nothing) where {T <: MIScalar}
+    n = LinearAlgebra.checksquare(A)
+    0 <= k <= 16 || throw(ArgumentError("phi!: k must be in 0:16"))
+    length(out) == k + 1 || throw(DimensionMismatch("phi!: out has $(length(out)) matrices, k + 1 = $(k + 1)"))
+    all(o -> size(o) == (n, n), out) || throw(DimensionMismatch("phi!: every out[j] must be $(n)x$(n)"))
+    ptrs = Ptr{Cvoid}[o.ptr for o in out]
+    info = zeros(Int64, 8)      # Taylor degree, scalings, products, microseconds
+    GC.@preserve out check(ccall((:expv_mi_phi, lib), Cint,
+                                 (Ptr{Cvoid}, Cint, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Ptr{Cvoid}}, Int64, Cint, Ptr{Int64}),
+                                 ctx().h, dtype(T), n, k, A.ptr, ld(A), ptrs, max(n, 1), DEVICE, info), ctx().h)
+    out
+end
+ExponentialUtilities.phi(A::MIMatrix{T}, k::Integer; kwargs...) where {T <: MIScalar} =
+    ExponentialUtilities.phi!([MIArray{T}(undef, size(A)...) for _ in 0:k], A, k; kwargs...)
+
 # ---- operator: the contract of docs/src/interfaces.md:7-36 (eltype, size, mul!, ishermitian, opnorm) --------------
 mutable struct MIOperator{T}
     h::Ptr{Cvoid}
