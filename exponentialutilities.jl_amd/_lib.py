@@ -101,6 +101,8 @@ PROTOTYPES = {
     "expv_mi_op_apply": (_i, [_vp, _vp, _i, _vp, _i]),
     "expv_mi_gemv_block": (_i, [_vp, _i, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i]),
     "expv_mi_expm": (_i, [_vp, _i, _i64, _vp, _i64, _i, _vp]),
+    "expv_mi_expm_balanced": (_i, [_vp, _i, _i64, _vp, _i64, _i, _vp]),
+    "expv_mi_gebal": (_i, [_vp, _i, _i64, _vp, _i64, _i, _vp, _vp, _vp]),
     "expv_mi_phi": (_i, [_vp, _i, _i64, _i, _vp, _i64, _vp, _i64, _i, _vp]),
     "expv_mi_gemm": (_i, [_vp, _i, _i64, _i64, _i64, _d, _d, _vp, _i64, _vp, _i64, _d, _d, _vp, _i64]),
     "expv_mi_ks_create": (_i, [_vp, _i, _i, _i64, _i, _i, _pvp]),
@@ -143,6 +145,7 @@ PROTOTYPES = {
     "expv_mi_host_rcm": (_i, [C.c_int64, _vp, _vp, _i, _vp, _vp]),
     "expv_mi_host_wrapsum": (_i, [_vp, C.c_uint64, _vp]),
     "expv_mi_host_expm": (_i, [_i, _i, _vp, _i]),
+    "expv_mi_host_gebal": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp]),
     "expv_mi_host_symtridiag_expcol": (_i, [_i, _pd, _pd, _d, _d, _pd]),
     "expv_mi_host_symtridiag_exp_last": (_i, [_i, _pd, _pd, _d, _d, _pd]),
     "expv_mi_host_phiv_dense": (_i, [_i, _i, _i, _vp, _i, _vp, _vp]),

@@ -30,7 +30,7 @@ __all__ = [
     "Context", "default_context", "MIOperator", "DeviceArray", "KrylovSubspace", "arnoldi", "arnoldi_",
     "lanczos_", "expv", "expv_", "phiv", "phiv_", "expv_timestep", "expv_timestep_", "phiv_timestep",
     "phiv_timestep_", "kiops", "timestep_caches", "expv_batch", "expv_batch_multi", "RcclComm", "rccl_available", "rccl_unique_id", "ExpvMIError", "DimensionMismatch", "host_expm",
-    "exponential", "exponential_", "mul_", "phi", "phi_",
+    "exponential", "exponential_", "mul_", "phi", "phi_", "balance_", "host_gebal",
     "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
 ]
 
@@ -1286,21 +1286,25 @@ def _square(shape, what):
 
 
 _EXPM_INFO = ("order", "squarings", "row_exchanges", "microseconds")
+_EXPM_BALANCE_INFO = _EXPM_INFO + ("ilo", "ihi", "sweeps", "balance_microseconds")
 
 
-def exponential_(A, ctx=None, return_info=False):
+def exponential_(A, balance=False, ctx=None, return_info=False):
     """exponential!(A) for a dense matrix, computed on the device whatever its size (exp.jl:56-58 -> ExpMethodHigham2005(false),
-    no balancing; expv_mi_expm).  A: a 2-D torch tensor on the GPU or a DeviceArray (used in place) or a numpy array (staged
-    through HBM, result copied back).  Row-major (C-contiguous) storage is passed as it is -- exp(A') = exp(A)' --, column-major
-    storage with its own leading dimension, any other stride pattern through a copy.  Returns A (and, with return_info, a dict:
-    Pade order, squarings, row exchanges of the LU, microseconds)."""
+    no balancing; expv_mi_expm).  balance=True: exponential!(A, ExpMethodHigham2005Base()) -- gebal first, the norm taken after
+    it, unbalance at the end (expv_mi_expm_balanced): the one to take for badly scaled matrices.  A: a 2-D torch tensor on the
+    GPU or a DeviceArray (used in place) or a numpy array (staged through HBM, result copied back).  Row-major (C-contiguous)
+    storage is passed as it is -- exp(A') = exp(A)' --, column-major storage with its own leading dimension, any other stride
+    pattern through a copy.  Returns A (and, with return_info, a dict: Pade order, squarings, row exchanges of the LU,
+    microseconds; with balance also ilo, ihi, sweeps of the scaling loop and the microseconds of balancing)."""
     dt = _dense_np_dtype(A)
     shape = tuple(A.shape)
     n = _square(shape, "exponential!")
     info = (C.c_int64 * 8)()
 
     def run(c, ptr, lda, loc):
-        _check(L.load().expv_mi_expm(c._h, _code(dt), n, ptr, max(int(lda), n, 1), loc, info), c._h)
+        fn = L.load().expv_mi_expm_balanced if balance else L.load().expv_mi_expm
+        _check(fn(c._h, _code(dt), n, ptr, max(int(lda), n, 1), loc, info), c._h)
 
     if isinstance(A, DeviceArray):
         run(ctx or A.ctx, A.ptr, n, L.DEVICE)
@@ -1332,11 +1336,12 @@ def exponential_(A, ctx=None, return_info=False):
                 run(c, tmp.ctypes.data, n, L.HOST)
                 A[...] = tmp
     if return_info:
-        return A, dict(zip(_EXPM_INFO, (int(v) for v in info[:4])))
+        names = _EXPM_BALANCE_INFO if balance else _EXPM_INFO
+        return A, dict(zip(names, (int(v) for v in info[:len(names)])))
     return A
 
 
-def exponential(A, ctx=None, return_info=False):
+def exponential(A, balance=False, ctx=None, return_info=False):
     """exponential(A): a new array of A's kind holding exp(A) (see exponential_)."""
     _dense_np_dtype(A)
     if isinstance(A, DeviceArray):
@@ -1345,7 +1350,51 @@ def exponential(A, ctx=None, return_info=False):
         B = A.clone()
     else:
         B = np.array(A, order="F", copy=True)
-    return exponential_(B, ctx=ctx, return_info=return_info)
+    return exponential_(B, balance=balance, ctx=ctx, return_info=return_info)
+
+
+def balance_(A, ctx=None):
+    """LAPACK.gebal!('B', A) for a dense matrix, computed on the device (expv_mi_gebal): A is balanced in place -- a 2-D torch
+    tensor on the GPU, a DeviceArray or a numpy array (staged through HBM).  Balancing is not symmetric in A and A', so storage that
+    is not column-major goes through a column-major copy.  Returns (ilo, ihi, scale): 1-based bounds and LAPACK's scale vector
+    (float64: the factors inside ilo..ihi, the exchanged positions outside)."""
+    dt = _dense_np_dtype(A)
+    n = _square(tuple(A.shape), "balance!")
+    ilo, ihi = C.c_int64(1), C.c_int64(0)
+    scale = np.ones(n, dtype=np.float64)
+
+    def run(c, ptr, lda, loc):
+        _check(L.load().expv_mi_gebal(c._h, _code(dt), n, ptr, max(int(lda), n, 1), loc, C.byref(ilo), C.byref(ihi), scale.ctypes.data), c._h)
+
+    if isinstance(A, DeviceArray):
+        run(ctx or A.ctx, A.ptr, n, L.DEVICE)
+    elif _is_torch(A):
+        if not A.is_cuda:
+            raise TypeError("torch tensors must live on the GPU (or pass a numpy array)")
+        c = ctx or default_context()
+        if n > 0:
+            if n == 1 or (A.stride(0) == 1 and A.stride(1) >= n):
+                _torch_ready(A)
+                run(c, A.data_ptr(), A.stride(1) if n > 1 else 1, L.DEVICE)
+            else:
+                tmp = A.t().contiguous()          # the rows of tmp are the columns of A
+                _torch_ready(tmp)
+                run(c, tmp.data_ptr(), n, L.DEVICE)
+                if getattr(c, "_async_outputs", False):
+                    c.sync()
+                A.copy_(tmp.t())
+    else:
+        if not isinstance(A, np.ndarray):
+            raise TypeError("balance_ works in place: pass a numpy array, a torch GPU tensor or a DeviceArray")
+        c = ctx or default_context()
+        if n > 0:
+            if A.flags.f_contiguous and A.flags.writeable:
+                run(c, A.ctypes.data, n, L.HOST)
+            else:
+                tmp = np.array(A, order="F", copy=True)
+                run(c, tmp.ctypes.data, n, L.HOST)
+                A[...] = tmp
+    return int(ilo.value), int(ihi.value), scale
 
 
 PHI_MAX_K = 16
@@ -1558,6 +1607,19 @@ def host_expm(A):
     n = A.shape[0]
     _check(L.load().expv_mi_host_expm(_HOST_CODES[A.dtype], n, A.ctypes.data, max(n, 1)))
     return A
+
+
+def host_gebal(A):
+    """LAPACK.gebal!('B', copy(A)) by the host routine behind host_expm (xGEBAL job 'B', in A's own element type; no GPU):
+    returns (balanced copy, ilo, ihi, scale)."""
+    A = np.array(A, dtype=_host_dtype(np.asarray(A).dtype), order="F", copy=True)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise DimensionMismatch(f"host_gebal: matrix is not square: dimensions are {A.shape}")
+    n = A.shape[0]
+    ilo, ihi = C.c_int64(1), C.c_int64(0)
+    scale = np.ones(n, dtype=np.float64)
+    _check(L.load().expv_mi_host_gebal(_HOST_CODES[A.dtype], n, A.ctypes.data, max(n, 1), C.byref(ilo), C.byref(ihi), scale.ctypes.data))
+    return A, int(ilo.value), int(ihi.value), scale
 
 
 def host_pattern_info(A, dtype=np.float64):

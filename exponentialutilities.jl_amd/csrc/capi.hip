@@ -1318,6 +1318,19 @@ void host_expm_T(int n, void *A, int lda) {
     for (int i = 0; i < n; ++i) reinterpret_cast<S *>(A)[(size_t)j * lda + i] = M(i, j);
 }
 template <class S>
+void host_gebal_T(int n, void *A, int lda, int64_t *ilo, int64_t *ihi, double *scale) {
+  Mat<S> M(n, n);
+  for (int j = 0; j < n; ++j)
+    for (int i = 0; i < n; ++i) M(i, j) = reinterpret_cast<S *>(A)[(size_t)j * lda + i];
+  const dense::Balance<S> B = dense::gebal(M);
+  for (int j = 0; j < n; ++j)
+    for (int i = 0; i < n; ++i) reinterpret_cast<S *>(A)[(size_t)j * lda + i] = M(i, j);
+  if (ilo) *ilo = B.ilo;
+  if (ihi) *ihi = B.ihi;
+  if (scale)
+    for (int i = 0; i < n; ++i) scale[i] = (double)B.scale[(size_t)i];
+}
+template <class S>
 void host_phiv_dense_T(int m, int k, const void *A, int lda, const void *v, void *w) {
   Mat<S> M(m, m);
   std::vector<S> vv(m);
@@ -1414,6 +1427,7 @@ int expv_mi_ctx_create(int device_id, void *stream, expv_mi_ctx_t *out) {
     std::unique_ptr<expv_mi_ctx_s> c(new expv_mi_ctx_s());
     c->device = device_id;
     c->opt = Options::from_env();
+    if (const char *e = std::getenv("EXPV_MI_DENSE_FORCE_SINGULAR")) c->dense_force_singular = std::atoi(e);  // test seam (dense_dev.hip)
     if (const char *e = std::getenv("EXPV_MI_DENSE_TILE")) c->dense_tile = std::atoi(e);      // developer A/B of the dense product's tiles
     HIPCHECK(hipSetDevice(device_id));
     if (stream) {
@@ -1965,7 +1979,8 @@ int expv_mi_gemv_block(expv_mi_ctx_t ctx, int dtype, int64_t nrows, int64_t ncol
 }
 
 // ------------------------------------------------------------------ dense matrices on the device ----------
-int expv_mi_expm(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t info[8]) {
+namespace {
+int expm_entry(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t info[8], bool balance) {
   return guarded(ctx, [&] {
     const auto t0 = std::chrono::steady_clock::now();
     check_device_dtype(dtype, "expm");
@@ -1981,10 +1996,39 @@ int expv_mi_expm(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, 
     DevBuf stage;
     int64_t ldd = lda;
     void *Ad = const_cast<void *>(stage_in_2d(ctx, A, loc, n, n, lda, esz, stage, &ldd));
-    dense_expm_run(ctx, dtype, n, Ad, ldd, info);
+    dense_expm_run(ctx, dtype, n, Ad, ldd, info, balance);
     if (loc == EXPV_MI_HOST) copy_out_2d(ctx, A, loc, lda, Ad, ldd, n, n, esz);
     else if (!ctx->async_out) HIPCHECK(hipStreamSynchronize(ctx->stream));
     if (info) info[3] = (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+  });
+}
+}  // namespace
+int expv_mi_expm(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t info[8]) {
+  return expm_entry(ctx, dtype, n, A, lda, loc, info, false);
+}
+int expv_mi_expm_balanced(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t info[8]) {
+  return expm_entry(ctx, dtype, n, A, lda, loc, info, true);
+}
+
+int expv_mi_gebal(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t *ilo, int64_t *ihi, double *scale_host) {
+  return guarded(ctx, [&] {
+    check_device_dtype(dtype, "gebal");
+    if (loc != EXPV_MI_HOST && loc != EXPV_MI_DEVICE) fail(EXPV_MI_ARGUMENT_ERROR, "gebal: unknown loc");
+    if (n < 0 || lda < n) fail(EXPV_MI_ARGUMENT_ERROR, "gebal: bad n / lda");
+    if (ilo) *ilo = 1;
+    if (ihi) *ihi = 0;
+    if (n == 0) return;
+    if (!A) fail(EXPV_MI_ARGUMENT_ERROR, "gebal: null pointer");
+    if (!ctx) fail(EXPV_MI_ARGUMENT_ERROR, "gebal: null context");
+    if (n > 65535) fail(EXPV_MI_UNSUPPORTED, "gebal: n > 65535");
+    ctx->use();
+    const size_t esz = dtype_size(dtype);
+    DevBuf stage;
+    int64_t ldd = lda;
+    void *Ad = const_cast<void *>(stage_in_2d(ctx, A, loc, n, n, lda, esz, stage, &ldd));
+    dense_gebal_run(ctx, dtype, n, Ad, ldd, ilo, ihi, scale_host, nullptr);
+    if (loc == EXPV_MI_HOST) copy_out_2d(ctx, A, loc, lda, Ad, ldd, n, n, esz);
+    else if (!ctx->async_out) HIPCHECK(hipStreamSynchronize(ctx->stream));
   });
 }
 
@@ -2546,6 +2590,18 @@ int expv_mi_host_expm(int dtype, int n, void *A, int lda) {
       case EXPV_MI_F32: host_expm_T<float>(n, A, lda); break;
       case EXPV_MI_C32: host_expm_T<dense::cf>(n, A, lda); break;
       default: fail(EXPV_MI_ARGUMENT_ERROR, "host_expm: unknown dtype");
+    }
+  });
+}
+int expv_mi_host_gebal(int dtype, int n, void *A, int lda, int64_t *ilo, int64_t *ihi, double *scale) {
+  return guarded(nullptr, [&] {
+    if (n < 0 || lda < n || (n > 0 && !A)) fail(EXPV_MI_ARGUMENT_ERROR, "host_gebal: bad n / lda / A");
+    switch (dtype) {
+      case EXPV_MI_F64: host_gebal_T<double>(n, A, lda, ilo, ihi, scale); break;
+      case EXPV_MI_C64: host_gebal_T<cd>(n, A, lda, ilo, ihi, scale); break;
+      case EXPV_MI_F32: host_gebal_T<float>(n, A, lda, ilo, ihi, scale); break;
+      case EXPV_MI_C32: host_gebal_T<dense::cf>(n, A, lda, ilo, ihi, scale); break;
+      default: fail(EXPV_MI_ARGUMENT_ERROR, "host_gebal: unknown dtype");
     }
   });
 }

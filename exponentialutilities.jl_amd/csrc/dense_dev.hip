@@ -20,6 +20,7 @@
 // (re: Ar Br - Ai Bi, im: Ar Bi + Ai Br), the minus sign applied to the Ai fragment after it is read.
 #include <chrono>
 #include <cmath>
+#include <limits>
 
 #include "engine.h"
 
@@ -587,8 +588,16 @@ void lu_solve_dev(Ctx *ctx, int64_t n, T *D, T *X, int32_t *ipiv, int32_t *stat)
 struct DenseWs {
   DevBuf W[6], colsum, ipiv, stat;
   DevBuf phiS, phiT;        // phi!(out, A, k): the slabs [Phi_0 ... Phi_k] and Phi_0 [Phi_0 ... Phi_k]
+  DevBuf bal;               // balancing: positions, counts, factors and the BalMeta words (carved by bal_carve)
   void *pin = nullptr;      // pinned host mirror of `stat`
-  ~DenseWs() { if (pin) (void)hipHostFree(pin); }
+  void *pinbal = nullptr;   // pinned host mirror of the BalMeta words
+  void *pinscale = nullptr; // pinned host mirror of rec[] and d[] (expv_mi_gebal's scale vector), grown on demand
+  size_t pinscale_bytes = 0;
+  ~DenseWs() {
+    if (pin) (void)hipHostFree(pin);
+    if (pinbal) (void)hipHostFree(pinbal);
+    if (pinscale) (void)hipHostFree(pinscale);
+  }
 };
 struct StatWords {      // device `stat` buffer / its host mirror
   double norm1;
@@ -605,8 +614,442 @@ DenseWs *dense_ws(Ctx *ctx) {
   return ws;
 }
 
+// ---------------------------------------------------------------------------------------------- balancing: xGEBAL job 'B' on the device
+// The decisions and their order are host_dense.h's gebal (2-norm variant, radix 2, factor 0.95), made by ONE workgroup; the n^2 work
+// around them is parallel.
+//   isolation  every exchange of the host routine is a symmetric permutation (the parts of the rows and columns it skips hold zeros),
+//              so the matrix is never moved during the search: the off-diagonal nonzeros of every row and column are counted once
+//              (-0.0 is zero), bal_peel walks the host's scan order on these counts and a position map pos[] (position -> original
+//              index) -- rows i = l .. 1 exchanged with l, then columns j = k .. l exchanged with k -- and lowers the counts by one
+//              column of A (or of its transpose) per isolated index.  P is applied once, by a gather (perm_scale).
+//   scaling    sequential in i as in LAPACK (each step sees the factors of the steps before it).  The matrix is not rewritten: a step
+//              reads column i of P'AP and of its transpose, scales every element by d_i / d_q (or d_q / d_i) on the fly -- exact,
+//              the factors are powers of two, so this is bit for bit the eagerly scaled element -- and sums the squares in fp64 for
+//              every element type, each thread over its own ascending rows, then lanes, then waves, always in the same order.
+//              The guards sfmin1/2, sfmax1/2 are those of the ELEMENT type's real type.
+//   loops      the peel runs at most n + 1 passes per phase, the sweeps at most BAL_MAX_SWEEPS (BalMeta.noconv still set then: the
+//              driver answers with a status), the two doubling loops of a step are bounded by their own guards.
+constexpr int BAL_THREADS = 512;
+constexpr int BAL_MAX_SWEEPS = 128;
+
+struct BalMeta {      // device words of one balancing / their pinned host mirror
+  int32_t ilo, ihi;   // 1-based, as LAPACK returns them
+  int32_t sweeps;     // sweeps of the scaling loop so far (the last one changes nothing)
+  int32_t noconv;     // the last sweep changed a factor
+  int32_t swaps;      // exchanges of two DIFFERENT positions
+  int32_t early;      // the l == 1 return of the row search (no column search, no scaling)
+};
+
+template <class T> __device__ inline bool nonzero_T(T a) { return re_of(a) != 0 || im_of(a) != 0; }
+
+// At = A' (plain transpose, no conjugation): packed n x n, through a 32 x 33 LDS tile so that both sides move along their columns
 template <class T>
-void expm_dev(Ctx *ctx, int64_t n, T *A, int64_t lda, int64_t info[8]) {
+__global__ __launch_bounds__(EW_THREADS) void transpose_to(const T *__restrict__ A, int64_t lda, int64_t n, T *__restrict__ At) {
+  __shared__ T tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int64_t r0 = (int64_t)blockIdx.x * 32, c0 = (int64_t)blockIdx.y * 32;
+  for (int j = ty; j < 32; j += EW_THREADS / 32)
+    if (r0 + tx < n && c0 + j < n) tile[j][tx] = A[(r0 + tx) + (c0 + j) * lda];
+  __syncthreads();
+  for (int j = ty; j < 32; j += EW_THREADS / 32)
+    if (c0 + tx < n && r0 + j < n) At[(c0 + tx) + (r0 + j) * n] = tile[tx][j];
+}
+
+// cnt[j] = number of nonzero entries of column j off the diagonal (one workgroup per column)
+template <class T>
+__global__ __launch_bounds__(EW_THREADS) void offdiag_count(const T *__restrict__ A, int64_t lda, int64_t n, int32_t *__restrict__ cnt) {
+  const int64_t j = blockIdx.x;
+  const T *col = A + j * lda;
+  int c = 0;
+  for (int64_t i = threadIdx.x; i < n; i += EW_THREADS)
+    if (i != j && nonzero_T(col[i])) ++c;
+  __shared__ int red[EW_THREADS];
+  red[threadIdx.x] = c;
+  __syncthreads();
+  for (int w = EW_THREADS / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) cnt[j] = red[0];
+}
+
+// The permutation phase (one workgroup).  rowcnt / colcnt: offdiag_count of A' and of A, by ORIGINAL index; they are lowered as
+// indices leave the active block.  Out: pos[], rec[] (LAPACK's record: rec[m] = 1 + the position exchanged with position m), d[] = dinv[] = 1,
+// and the meta words.  Positions are 0-based here, ilo / ihi 1-based.
+template <class T>
+__global__ __launch_bounds__(BAL_THREADS) void bal_peel(const T *__restrict__ A, int64_t lda, const T *__restrict__ At, int n, int32_t *rowcnt,
+                                                        int32_t *colcnt, int32_t *pos, double *rec, double *d, double *dinv, BalMeta *meta) {
+  __shared__ int found;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += BAL_THREADS) {
+    pos[i] = i;
+    rec[i] = 1.0;
+    d[i] = 1.0;
+    dinv[i] = 1.0;
+  }
+  __syncthreads();
+  int k = 1, l = n, swaps = 0;
+  bool early = false;
+  for (int pass = 0; pass <= n; ++pass) {      // rows that isolate an eigenvalue go to the bottom
+    bool any = false;
+    int cur = l - 1;
+    while (cur >= 0) {
+      int hit = -1;      // the largest position <= cur whose row has no off-diagonal nonzero in the columns 0 .. l-1
+      while (cur >= 0) {
+        if (tid == 0) found = -1;
+        __syncthreads();
+        const int p = cur - tid;
+        if (p >= 0 && rowcnt[pos[p]] == 0) atomicMax(&found, p);
+        __syncthreads();
+        const int f = found;
+        __syncthreads();
+        if (f >= 0) { hit = f; break; }
+        cur -= BAL_THREADS;
+      }
+      if (hit < 0) break;
+      const int o = pos[hit], ol = pos[l - 1];
+      __syncthreads();
+      if (tid == 0) {
+        pos[hit] = ol;
+        pos[l - 1] = o;
+        rec[l - 1] = (double)(hit + 1);
+      }
+      if (hit != l - 1) ++swaps;
+      any = true;
+      if (l == 1) { early = true; break; }
+      const T *col = A + (int64_t)o * lda;      // column o leaves the active block: one nonzero fewer in the rows that had one there
+      for (int i = tid; i < n; i += BAL_THREADS)
+        if (i != o && nonzero_T(col[i])) rowcnt[i] -= 1;
+      --l;
+      cur = hit - 1;
+      __syncthreads();
+    }
+    if (early || !any) break;
+  }
+  if (!early) {
+    for (int pass = 0; pass <= n; ++pass) {      // columns that isolate an eigenvalue go to the left
+      bool any = false;
+      int cur = k - 1;
+      while (cur <= l - 1) {
+        int hit = -1;      // the smallest position >= cur whose column has no off-diagonal nonzero in the rows k-1 .. l-1
+        while (cur <= l - 1) {
+          if (tid == 0) found = 0x7fffffff;
+          __syncthreads();
+          const int p = cur + tid;
+          if (p <= l - 1 && colcnt[pos[p]] == 0) atomicMin(&found, p);
+          __syncthreads();
+          const int f = found;
+          __syncthreads();
+          if (f != 0x7fffffff) { hit = f; break; }
+          cur += BAL_THREADS;
+        }
+        if (hit < 0) break;
+        const int o = pos[hit], ok = pos[k - 1];
+        __syncthreads();
+        if (tid == 0) {
+          pos[hit] = ok;
+          pos[k - 1] = o;
+          rec[k - 1] = (double)(hit + 1);
+        }
+        if (hit != k - 1) ++swaps;
+        any = true;
+        const T *row = At + (int64_t)o * n;      // row o leaves the active block
+        for (int i = tid; i < n; i += BAL_THREADS)
+          if (i != o && nonzero_T(row[i])) colcnt[i] -= 1;
+        ++k;
+        cur = hit + 1;
+        __syncthreads();
+      }
+      if (!any) break;
+    }
+  }
+  if (tid == 0) {
+    meta->ilo = early ? 1 : k;
+    meta->ihi = early ? 1 : l;
+    meta->sweeps = 0;
+    meta->noconv = early ? 0 : 1;
+    meta->swaps = swaps;
+    meta->early = early ? 1 : 0;
+  }
+}
+
+// wave-wide sum / first maximum by lane exchanges: every lane ends with the same value
+__device__ inline double bal_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+// (CX: the winning element travels along -- its modulus is needed afterwards; for the real types the weight IS the modulus)
+template <bool CX>
+__device__ inline void bal_wave_first_max(double &w, int &wi, double &re, double &im) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double ow = __shfl_xor(w, off);
+    const int oi = __shfl_xor(wi, off);
+    double ore = 0.0, oim = 0.0;
+    if constexpr (CX) { ore = __shfl_xor(re, off); oim = __shfl_xor(im, off); }
+    if (ow > w || (ow == w && oi < wi)) { w = ow; wi = oi; re = ore; im = oim; }
+  }
+}
+// workgroup-wide sum / maximum through buf[BAL_THREADS / 64] (two barriers; every thread returns the same value)
+__device__ inline double bal_block_sum(double v, double *buf) {
+  v = bal_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int w = 0; w < BAL_THREADS / 64; ++w) s += buf[w];
+  __syncthreads();
+  return s;
+}
+__device__ inline double bal_block_max(double v, double *buf) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = buf[0];
+#pragma unroll
+  for (int w = 1; w < BAL_THREADS / 64; ++w) s = fmax(s, buf[w]);
+  __syncthreads();
+  return s;
+}
+// 2-norm of vec[lo .. hi] with every element times num / d[q] (INV = false) or d[q] / num (INV = true), in the scaled form: only
+// where the plain sum of squares leaves (1e-280, 1e280) -- nrm2_strided of the host routine.  dinv[q] = 1 / d[q], inum = 1 / num.
+template <class T, bool INV>
+__device__ inline double bal_nrm2_scaled(const T *__restrict__ vec, int lo, int hi, const double *d, const double *dinv, double num, double inum,
+                                         double *buf) {
+  double amax = 0.0;
+  for (int q = lo + (int)threadIdx.x; q <= hi; q += BAL_THREADS) {
+    const double ratio = INV ? d[q] * inum : num * dinv[q];
+    amax = fmax(amax, fmax(fabs((double)re_of(vec[q]) * ratio), fabs((double)im_of(vec[q]) * ratio)));
+  }
+  amax = bal_block_max(amax, buf);
+  if (!(amax > 0.0)) return 0.0;
+  double ssq = 0.0;
+  for (int q = lo + (int)threadIdx.x; q <= hi; q += BAL_THREADS) {
+    const double ratio = INV ? d[q] * inum : num * dinv[q];
+    const double re = (double)re_of(vec[q]) * ratio / amax, im = (double)im_of(vec[q]) * ratio / amax;
+    ssq += re * re + im * im;
+  }
+  return amax * sqrt(bal_block_sum(ssq, buf));
+}
+
+// The sweeps of the scaling loop (at most BAL_MAX_SWEEPS) over the positions ilo .. ihi (one workgroup).  Ap = P'AP and Apt = its transpose, both
+// packed; d[] holds the factors (1 outside ilo .. ihi), dinv[] their reciprocals: the only things written, with the sweep count and
+// `noconv`.  d_i / d_q is formed as d_i * (1 / d_q): both are powers of two, so the product is the quotient bit for bit.
+template <class T>
+__global__ __launch_bounds__(BAL_THREADS) void bal_sweeps(const T *__restrict__ Ap, const T *__restrict__ Apt, int n, double *d, double *dinv, BalMeta *meta,
+                                                          double sfmin1, double sfmax1, double sfmin2, double sfmax2) {
+  constexpr int NW = BAL_THREADS / 64;
+  constexpr bool CX = ST<T>::is_complex;
+  __shared__ double s_ssc[NW], s_ssr[NW], s_bc[NW], s_br[NW], s_buf[NW], s_el[4][NW];
+  __shared__ int s_ic[NW], s_ir[NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k0 = meta->ilo - 1, l0 = meta->ihi - 1;      // first and last active position
+  int sweeps = meta->sweeps, noconv = meta->noconv;
+  __syncthreads();
+  while (noconv && sweeps < BAL_MAX_SWEEPS) {
+    noconv = 0;
+    for (int i = k0; i <= l0; ++i) {
+      const double di = d[i], dii = dinv[i];
+      const T *col = Ap + (int64_t)i * n, *row = Apt + (int64_t)i * n;
+      double ssc = 0.0, ssr = 0.0, bc = -1.0, br = -1.0, cre = 0.0, cim = 0.0, rre = 0.0, rim = 0.0;
+      int ic = 0x7fffffff, ir = 0x7fffffff;
+      for (int q = tid; q <= l0; q += BAL_THREADS) {      // column i: rows 0 .. ihi-1 for the largest entry, ilo-1 .. ihi-1 for the norm
+        const double ratio = di * dinv[q];
+        const double re = (double)re_of(col[q]) * ratio, im = (double)im_of(col[q]) * ratio;
+        const double w = fabs(re) + fabs(im);
+        if (w > bc) { bc = w; ic = q; cre = re; cim = im; }
+        if (q >= k0) ssc += re * re + im * im;
+      }
+      for (int q = k0 + tid; q < n; q += BAL_THREADS) {   // row i: columns ilo-1 .. n-1 for the largest entry, ilo-1 .. ihi-1 for the norm
+        const double ratio = d[q] * dii;
+        const double re = (double)re_of(row[q]) * ratio, im = (double)im_of(row[q]) * ratio;
+        const double w = fabs(re) + fabs(im);
+        if (w > br) { br = w; ir = q; rre = re; rim = im; }
+        if (q <= l0) ssr += re * re + im * im;
+      }
+      ssc = bal_wave_sum(ssc);
+      ssr = bal_wave_sum(ssr);
+      bal_wave_first_max<CX>(bc, ic, cre, cim);
+      bal_wave_first_max<CX>(br, ir, rre, rim);
+      if (lane == 0) {
+        s_ssc[wave] = ssc; s_ssr[wave] = ssr;
+        s_bc[wave] = bc; s_ic[wave] = ic;
+        s_br[wave] = br; s_ir[wave] = ir;
+        if constexpr (CX) { s_el[0][wave] = cre; s_el[1][wave] = cim; s_el[2][wave] = rre; s_el[3][wave] = rim; }
+      }
+      __syncthreads();
+      ssc = s_ssc[0]; ssr = s_ssr[0]; bc = s_bc[0]; ic = s_ic[0]; br = s_br[0]; ir = s_ir[0];
+      int wc = 0, wr = 0;      // the waves that hold the two first maxima
+#pragma unroll
+      for (int w = 1; w < NW; ++w) {
+        ssc += s_ssc[w];
+        ssr += s_ssr[w];
+        if (s_bc[w] > bc || (s_bc[w] == bc && s_ic[w] < ic)) { bc = s_bc[w]; ic = s_ic[w]; wc = w; }
+        if (s_br[w] > br || (s_br[w] == br && s_ir[w] < ir)) { br = s_br[w]; ir = s_ir[w]; wr = w; }
+      }
+      double c = (ssc > 1e-280 && ssc < 1e280) ? sqrt(ssc) : bal_nrm2_scaled<T, false>(col, k0, l0, d, dinv, di, dii, s_buf);
+      double r = (ssr > 1e-280 && ssr < 1e280) ? sqrt(ssr) : bal_nrm2_scaled<T, true>(row, k0, l0, d, dinv, di, dii, s_buf);
+      double f = 1.0;
+      bool change = false;
+      if (c != 0.0 && r != 0.0) {
+        double ca = bc, ra = br;      // the modulus of the entry with the largest |re| + |im| (the first one)
+        if constexpr (CX) {
+          ca = hypot(s_el[0][wc], s_el[1][wc]);
+          ra = hypot(s_el[2][wr], s_el[3][wr]);
+        }
+        double g = r / 2.0;
+        const double s = c + r;
+        while (c < g && fmax(f, fmax(c, ca)) < sfmax2 && fmin(r, fmin(g, ra)) > sfmin2) {
+          f *= 2.0; c *= 2.0; ca *= 2.0; r /= 2.0; g /= 2.0; ra /= 2.0;
+        }
+        g = c / 2.0;
+        while (g >= r && fmax(r, ra) < sfmax2 && fmin(fmin(f, c), fmin(g, ca)) > sfmin2) {
+          f /= 2.0; c /= 2.0; g /= 2.0; ca /= 2.0; r *= 2.0; ra *= 2.0;
+        }
+        change = !((c + r) >= 0.95 * s) && !(f < 1.0 && di < 1.0 && f * di <= sfmin1) && !(f > 1.0 && di > 1.0 && di >= sfmax1 / f);
+      }
+      if (change) {
+        noconv = 1;
+        if (tid == 0) {
+          d[i] = di * f;
+          dinv[i] = 1.0 / (di * f);
+        }
+      }
+      __syncthreads();      // d[i] is visible to the next step, the LDS slots are free again
+    }
+    ++sweeps;
+  }
+  if (tid == 0) {
+    meta->sweeps = sweeps;
+    meta->noconv = noconv;
+  }
+}
+
+// by position q and by original index o = pos[q]: the inverse map and the four factor vectors of the two element-wise passes
+__global__ __launch_bounds__(EW_THREADS) void bal_factors(const int32_t *__restrict__ pos, const double *__restrict__ d, int64_t n, int32_t *__restrict__ inv,
+                                                          double *__restrict__ rf, double *__restrict__ cf, double *__restrict__ urf,
+                                                          double *__restrict__ ucf) {
+  const int64_t q = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x;
+  if (q >= n) return;
+  const int32_t o = pos[q];
+  const double dq = d[q];
+  inv[o] = (int32_t)q;
+  rf[q] = 1.0 / dq;      // A_bal[i, j] = (P'AP)[i, j] d_j / d_i
+  cf[q] = dq;
+  urf[o] = dq;           // exp(A)[i, j] = X[inv i, inv j] d_(inv i) / d_(inv j)
+  ucf[o] = 1.0 / dq;
+}
+
+template <class R> __device__ inline R scale_pow2(R x, double fac) { return (R)((double)x * fac); }
+
+// dst[i, j] = src[map[i], map[j]] rf[i] cf[j]  (blockIdx.y = column j).  map == nullptr: the identity, and then 16-byte packs where
+// both columns are aligned; rf == nullptr: no factors (a pure gather).  rf[i] cf[j] is one power of two in fp64 and the product is
+// rounded to the element type once, so the result is the exactly scaled element.  dst == src is allowed when map == nullptr.
+// (For the fp64 element types rf[i] cf[j] itself can leave the double range -- factors 2^600 apart and more -- where the host's
+// step-by-step scaling of a small enough entry would not; the guards keep each factor inside (sfmin1, sfmax1), not their quotient.)
+template <class T>
+__global__ __launch_bounds__(EW_THREADS) void perm_scale(const T *src, int64_t lds_, T *dst, int64_t ldd, int64_t n, const int32_t *__restrict__ map,
+                                                         const double *__restrict__ rf, const double *__restrict__ cf) {
+  using R = typename ST<T>::real_t;
+  constexpr int NP = ST<T>::nreal, N = Pack<R>::N;
+  const int64_t j = blockIdx.y;
+  const int64_t t = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x, nt = (int64_t)gridDim.x * EW_THREADS;
+  const double cj = rf ? cf[j] : 1.0;
+  R *d = reinterpret_cast<R *>(dst + j * ldd);
+  if (map) {
+    const R *s = reinterpret_cast<const R *>(src + (int64_t)map[j] * lds_);
+    for (int64_t i = t; i < n; i += nt) {
+      const int64_t si = map[i];
+      const double fac = rf ? rf[i] * cj : 1.0;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) d[i * NP + p] = rf ? scale_pow2<R>(s[si * NP + p], fac) : s[si * NP + p];
+    }
+    return;
+  }
+  const R *s = reinterpret_cast<const R *>(src + j * lds_);
+  const int64_t len = n * NP;
+  int64_t done = 0;
+  if (aligned16(s) && aligned16(d)) {
+    const int64_t np = len / N;
+    for (int64_t i = t; i < np; i += nt) {
+      Pack<R> p = reinterpret_cast<const Pack<R> *>(s)[i];
+      if (rf) {
+#pragma unroll
+        for (int q = 0; q < N; ++q) p.v[q] = scale_pow2<R>(p.v[q], rf[(i * N + q) / NP] * cj);
+      }
+      reinterpret_cast<Pack<R> *>(d)[i] = p;
+    }
+    done = np * N;
+  }
+  for (int64_t e = done + t; e < len; e += nt) d[e] = rf ? scale_pow2<R>(s[e], rf[e / NP] * cj) : s[e];
+}
+
+struct BalBufs {      // the carved `bal` buffer of the workspace
+  int32_t *pos, *inv, *rowcnt, *colcnt;
+  double *rec, *d, *dinv, *rf, *cf, *urf, *ucf;
+  BalMeta *meta;
+};
+BalBufs bal_carve(DenseWs *ws, int64_t n) {
+  const size_t ni = (((size_t)n * sizeof(int32_t) + 255) / 256) * 256, nd = (((size_t)n * sizeof(double) + 255) / 256) * 256;
+  const size_t bytes = 4 * ni + 7 * nd + 256;
+  if (ws->bal.bytes < bytes) ws->bal.alloc(bytes);
+  if (!ws->pinbal) HIPCHECK(hipHostMalloc(&ws->pinbal, sizeof(BalMeta), hipHostMallocDefault));
+  char *p = ws->bal.as<char>();
+  BalBufs b;
+  b.pos = reinterpret_cast<int32_t *>(p);
+  b.inv = reinterpret_cast<int32_t *>(p + ni);
+  b.rowcnt = reinterpret_cast<int32_t *>(p + 2 * ni);
+  b.colcnt = reinterpret_cast<int32_t *>(p + 3 * ni);
+  p += 4 * ni;
+  b.rec = reinterpret_cast<double *>(p);
+  b.d = reinterpret_cast<double *>(p + nd);
+  b.rf = reinterpret_cast<double *>(p + 2 * nd);
+  b.cf = reinterpret_cast<double *>(p + 3 * nd);
+  b.urf = reinterpret_cast<double *>(p + 4 * nd);
+  b.ucf = reinterpret_cast<double *>(p + 5 * nd);
+  b.dinv = reinterpret_cast<double *>(p + 6 * nd);
+  b.meta = reinterpret_cast<BalMeta *>(p + 7 * nd);
+  return b;
+}
+
+template <class T>
+dim3 column_grid(int64_t n) {
+  using R = typename ST<T>::real_t;
+  return dim3((unsigned)std::min<int64_t>((n * ST<T>::nreal / Pack<R>::N + EW_THREADS) / EW_THREADS, 64), (unsigned)n);
+}
+
+// Balances A (device, leading dimension lda; only read): afterwards Ap holds P'AP (packed, NOT yet scaled), the factor vectors of
+// `b` are complete and the meta words are on their way to the pinned mirror -- the caller synchronises the stream before it reads
+// them.  At and Apt are scratch (packed n x n).  The sweeps loop inside ONE launch, capped at BAL_MAX_SWEEPS: one launch per sweep with
+// `noconv` read back in between was measured too and was slower or equal (profiles/expm_balance_sweep_forms.txt), so it is gone.
+template <class T>
+void balance_dev(Ctx *ctx, DenseWs *ws, const BalBufs &b, int64_t n, const T *A, int64_t lda, T *At, T *Ap, T *Apt) {
+  using R = typename ST<T>::real_t;
+  hipStream_t s = ctx->stream;
+  BalMeta *hmeta = reinterpret_cast<BalMeta *>(ws->pinbal);
+  const dim3 tgrid((unsigned)((n + 31) / 32), (unsigned)((n + 31) / 32)), cgrid = column_grid<T>(n);
+  transpose_to<T><<<tgrid, EW_THREADS, 0, s>>>(A, lda, n, At);
+  offdiag_count<T><<<(unsigned)n, EW_THREADS, 0, s>>>(A, lda, n, b.colcnt);
+  offdiag_count<T><<<(unsigned)n, EW_THREADS, 0, s>>>(At, n, n, b.rowcnt);
+  bal_peel<T><<<1, BAL_THREADS, 0, s>>>(A, lda, At, (int)n, b.rowcnt, b.colcnt, b.pos, b.rec, b.d, b.dinv, b.meta);
+  perm_scale<T><<<cgrid, EW_THREADS, 0, s>>>(A, lda, Ap, n, n, b.pos, nullptr, nullptr);
+  perm_scale<T><<<cgrid, EW_THREADS, 0, s>>>(At, n, Apt, n, n, b.pos, nullptr, nullptr);
+  HIPCHECK(hipGetLastError());
+  const double tiny = (double)std::numeric_limits<R>::min(), eps = (double)std::numeric_limits<R>::epsilon();
+  const double sfmin1 = tiny / eps, sfmax1 = 1.0 / sfmin1, sfmin2 = sfmin1 * 2.0, sfmax2 = 1.0 / sfmin2;
+  bal_sweeps<T><<<1, BAL_THREADS, 0, s>>>(Ap, Apt, (int)n, b.d, b.dinv, b.meta, sfmin1, sfmax1, sfmin2, sfmax2);
+  bal_factors<<<(unsigned)((n + EW_THREADS - 1) / EW_THREADS), EW_THREADS, 0, s>>>(b.pos, b.d, n, b.inv, b.rf, b.cf, b.urf, b.ucf);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(hmeta, b.meta, sizeof(BalMeta), hipMemcpyDeviceToHost, s));
+}
+void bal_check_settled(const BalMeta *hmeta) {
+  if (hmeta->noconv) fail(EXPV_MI_UNSUPPORTED, "gebal: the scaling loop did not settle in 128 sweeps");
+}
+
+template <class T>
+void expm_dev(Ctx *ctx, int64_t n, T *A, int64_t lda, int64_t info[8], bool balance) {
   using R = typename ST<T>::real_t;
   constexpr int NP = ST<T>::nreal;
   hipStream_t s = ctx->stream;
@@ -627,8 +1070,36 @@ void expm_dev(Ctx *ctx, int64_t n, T *A, int64_t lda, int64_t info[8]) {
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipMemcpyAsync(hstat, dstat, sizeof(StatWords), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  const double nA = hstat->norm1;
+  double nA = hstat->norm1;
   if (!std::isfinite(nA)) fail(EXPV_MI_ARGUMENT_ERROR, "ArgumentError: matrix contains Infs or NaNs");
+
+  // ExpMethodHigham2005Base: balance first, and take the norm AFTER balancing (exp_baseexp.jl:127-129, host_dense.h) -- the one
+  // deliberate difference to exp_noalloc.jl:117.  The balanced matrix lands in W[2]; everything below reads it from there.
+  const T *src = A;
+  int64_t ld_src = lda;
+  BalBufs bb{};
+  const BalMeta *hmeta = nullptr;
+  int64_t bal_us = 0;
+  if (balance) {
+    const auto t0 = std::chrono::steady_clock::now();
+    bb = bal_carve(ws, n);
+    hmeta = reinterpret_cast<const BalMeta *>(ws->pinbal);
+    T *At = ws->W[1].as<T>(), *Ap = ws->W[2].as<T>(), *Apt = ws->W[3].as<T>();
+    balance_dev<T>(ctx, ws, bb, n, A, lda, At, Ap, Apt);
+    perm_scale<T><<<column_grid<T>(n), EW_THREADS, 0, s>>>(Ap, n, Ap, n, n, nullptr, bb.rf, bb.cf);
+    HIPCHECK(hipMemsetAsync(dstat, 0, sizeof(StatWords), s));
+    colsum_abs<T><<<(unsigned)n, EW_THREADS, 0, s>>>(Ap, n, n, ws->colsum.as<double>());
+    colsum_max<<<1, EW_THREADS, 0, s>>>(ws->colsum.as<double>(), n, &dstat->norm1);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(hstat, dstat, sizeof(StatWords), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    bal_check_settled(hmeta);
+    nA = hstat->norm1;
+    if (!std::isfinite(nA)) fail(EXPV_MI_ARGUMENT_ERROR, "ArgumentError: matrix contains Infs or NaNs");
+    src = Ap;
+    ld_src = n;
+    bal_us += (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+  }
 
   const double *Cf;
   int N, si = 0;
@@ -651,7 +1122,7 @@ void expm_dev(Ctx *ctx, int64_t n, T *A, int64_t lda, int64_t info[8]) {
   const dim3 col_grid((unsigned)std::min<int64_t>((n * NP / Pack<R>::N + EW_THREADS) / EW_THREADS, 64), (unsigned)n);
   auto mm = [&](T *Cm, const T *X, const T *Y) { gemm_dev<T>(ctx, n, n, n, one, X, n, Y, n, zero, true, Cm, n); };
 
-  copy_scale<T><<<col_grid, EW_THREADS, 0, s>>>(A, lda, As, n, n, (R)std::ldexp(1.0, -si));
+  copy_scale<T><<<col_grid, EW_THREADS, 0, s>>>(src, ld_src, As, n, n, (R)std::ldexp(1.0, -si));
   HIPCHECK(hipGetLastError());
   mm(A2, As, As);
   const T *Pk = A2;      // A2^k
@@ -677,20 +1148,73 @@ void expm_dev(Ctx *ctx, int64_t n, T *A, int64_t lda, int64_t info[8]) {
   // the exchange count and the zero-pivot flag come back together; nothing has touched the caller's matrix yet
   HIPCHECK(hipMemcpyAsync(hstat, dstat, sizeof(StatWords), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  if (hstat->lu[1] != 0) throw dense::SingularError();
-  copy_scale<T><<<col_grid, EW_THREADS, 0, s>>>(X, n, A, lda, n, (R)1);
-  HIPCHECK(hipGetLastError());
+  // (dense_force_singular: a host-side seam for the tests -- no finite matrix reaches an exactly zero pivot column)
+  if (hstat->lu[1] != 0 || ctx->dense_force_singular) throw dense::SingularError();
+  if (!balance) {
+    copy_scale<T><<<col_grid, EW_THREADS, 0, s>>>(X, n, A, lda, n, (R)1);
+    HIPCHECK(hipGetLastError());
+  } else {      // the copy-out IS unbalance: the scaling undone, then the exchanges in reverse (the inverse map), in one pass
+    const auto t0 = std::chrono::steady_clock::now();
+    perm_scale<T><<<col_grid, EW_THREADS, 0, s>>>(X, n, A, lda, n, hmeta->swaps ? bb.inv : nullptr, bb.urf, bb.ucf);
+    HIPCHECK(hipGetLastError());
+    if (!ctx->async_out) HIPCHECK(hipStreamSynchronize(s));
+    bal_us += (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+  }
   if (info) {
     info[0] = N - 1;
     info[1] = si;
     info[2] = hstat->lu[0];
+    if (balance) {
+      info[4] = hmeta->ilo;
+      info[5] = hmeta->ihi;
+      info[6] = hmeta->sweeps;
+      info[7] = bal_us;
+    }
   }
+}
+
+template <class T> double norm1_to_host(Ctx *ctx, DenseWs *ws, const T *A, int64_t lda, int64_t n);
+
+// LAPACK.gebal!('B', A) for a device matrix: A balanced in place, ilo / ihi 1-based, scale_host in LAPACK's convention (the factors
+// inside ilo .. ihi, 1 + the exchanged position outside).  Complete on return but for the last pass over A (stream-ordered).
+template <class T>
+void gebal_dev(Ctx *ctx, int64_t n, T *A, int64_t lda, int64_t *ilo, int64_t *ihi, double *scale_host, int64_t *sweeps) {
+  hipStream_t s = ctx->stream;
+  DenseWs *ws = dense_ws(ctx);
+  auto need = [&](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
+  const size_t mat_bytes = ((sizeof(T) * (size_t)n * (size_t)n + 255) / 256) * 256;
+  for (int w = 1; w <= 3; ++w) need(ws->W[w], mat_bytes);
+  const double nA = norm1_to_host<T>(ctx, ws, A, lda, n);      // LAPACK.gebal!'s chkfinite
+  if (!std::isfinite(nA)) fail(EXPV_MI_ARGUMENT_ERROR, "ArgumentError: matrix contains Infs or NaNs");
+  const BalBufs bb = bal_carve(ws, n);
+  const BalMeta *hmeta = reinterpret_cast<const BalMeta *>(ws->pinbal);
+  T *Ap = ws->W[2].as<T>();
+  balance_dev<T>(ctx, ws, bb, n, A, lda, ws->W[1].as<T>(), Ap, ws->W[3].as<T>());
+  if (ws->pinscale_bytes < 2 * sizeof(double) * (size_t)n) {
+    if (ws->pinscale) (void)hipHostFree(ws->pinscale);
+    ws->pinscale = nullptr;
+    ws->pinscale_bytes = 0;
+    HIPCHECK(hipHostMalloc(&ws->pinscale, 2 * sizeof(double) * (size_t)n, hipHostMallocDefault));
+    ws->pinscale_bytes = 2 * sizeof(double) * (size_t)n;
+  }
+  const double *rec = reinterpret_cast<const double *>(ws->pinscale), *d = rec + n;
+  HIPCHECK(hipMemcpyAsync(ws->pinscale, bb.rec, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(reinterpret_cast<double *>(ws->pinscale) + n, bb.d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  bal_check_settled(hmeta);
+  perm_scale<T><<<column_grid<T>(n), EW_THREADS, 0, s>>>(Ap, n, A, lda, n, nullptr, bb.rf, bb.cf);
+  HIPCHECK(hipGetLastError());
+  if (ilo) *ilo = hmeta->ilo;
+  if (ihi) *ihi = hmeta->ihi;
+  if (sweeps) *sweeps = hmeta->sweeps;
+  if (scale_host)
+    for (int64_t q = 0; q < n; ++q) scale_host[q] = (q + 1 >= hmeta->ilo && q + 1 <= hmeta->ihi) ? d[q] : rec[q];
 }
 
 // ---------------------------------------------------------------------------------------------- phi!(out, A, k)
 // phi_0(A) ... phi_k(A) of a device matrix (phi.jl:159-257) by scaling and recovering: s = smallest integer with |A|_1 2^-s <= 1,
 // phi_k(As) by its Taylor series to degree M (Paterson-Stockmeyer, tau = 4), phi_j(As) = As phi_{j+1}(As) + I / j! downwards, then s
-// times phi_0(2X) = phi_0(X)^2, phi_j(2X) = 2^-j (phi_0(X) phi_j(X) + sum_{i=1..j} phi_i(X) / (j - i)!).  DESIGN.md 4.1.2 derives
+// times phi_0(2X) = phi_0(X)^2, phi_j(2X) = 2^-j (phi_0(X) phi_j(X) + sum_{i=1..j} phi_i(X) / (j - i)!).  DESIGN.md 4.1.1 derives
 // M (18 for the 64-bit types, 10 for the 32-bit ones: the remainder at |As|_1 <= 1 is below the unit roundoff for every k) and
 // counts the products: tau - 1 = 3 powers, M / tau Horner steps (4 or 2), k for the recurrence, one WIDE product per recovery step.
 constexpr int PHI_MAX_K = 16;
@@ -939,10 +1463,17 @@ void dense_gemm_run(Ctx *ctx, int dtype, int64_t m, int64_t n, int64_t k, double
   });
 }
 
-void dense_expm_run(Ctx *ctx, int dtype, int64_t n, void *A_dev, int64_t lda, int64_t info[8]) {
+void dense_expm_run(Ctx *ctx, int dtype, int64_t n, void *A_dev, int64_t lda, int64_t info[8], bool balance) {
   dispatch_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    expm_dev<T>(ctx, n, reinterpret_cast<T *>(A_dev), lda, info);
+    expm_dev<T>(ctx, n, reinterpret_cast<T *>(A_dev), lda, info, balance);
+  });
+}
+
+void dense_gebal_run(Ctx *ctx, int dtype, int64_t n, void *A_dev, int64_t lda, int64_t *ilo, int64_t *ihi, double *scale_host, int64_t *sweeps) {
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    gebal_dev<T>(ctx, n, reinterpret_cast<T *>(A_dev), lda, ilo, ihi, scale_host, sweeps);
   });
 }
 

@@ -155,6 +155,7 @@ struct Ctx {
   void (*ws_batch_free)(void *) = nullptr;
   void *ws_dense = nullptr;   // workspace of the dense device exponential: six n x n matrices + pivots (owned; dense_dev.hip)
   void (*ws_dense_free)(void *) = nullptr;
+  int dense_force_singular = 0; // test seam: the dense exponentials answer SingularException after the solve, as if the LU had met a zero pivot column (EXPV_MI_DENSE_FORCE_SINGULAR at creation)
   int dense_tile = 0;         // tile of the dense product kernel: 0 by size, 1 small, 2 big (EXPV_MI_DENSE_TILE at creation; A/B of tools/expm_device.py)
   // cumulative counters (expv_mi_ctx_counters): what ran, and whether a bounded device wait ever expired
   int64_t cnt_steps = 0, cnt_fact = 0, cnt_live = 0, cnt_serial_redo = 0, cnt_wave_redo = 0, cnt_opapply = 0, cnt_pipe = 0, cnt_copy = 0;
@@ -524,7 +525,12 @@ void dense_gemm_run(Ctx *ctx, int dtype, int64_t m, int64_t n, int64_t k, double
                     const void *B, int64_t ldb, double beta_re, double beta_im, void *C, int64_t ldc);
 // exponential!(A) of a device matrix in place (Higham 2005 without balancing); info[0..2] = Pade order, squarings, row exchanges.
 // Synchronises the stream twice (norm; LU status) and leaves the copy into A enqueued.
-void dense_expm_run(Ctx *ctx, int dtype, int64_t n, void *A_dev, int64_t lda, int64_t info[8]);
+// balance: ExpMethodHigham2005Base -- gebal first, the norm taken after it, unbalance folded into the copy into A; info[4..7] = ilo,
+// ihi, sweeps, microseconds of balancing (one more synchronisation: the balanced norm and the balancing's meta words).
+void dense_expm_run(Ctx *ctx, int dtype, int64_t n, void *A_dev, int64_t lda, int64_t info[8], bool balance = false);
+// LAPACK.gebal!('B', A) of a device matrix in place; scale_host: n doubles on the host (LAPACK's convention).  Synchronises the stream
+// (finite check; meta words) and leaves the last pass over A enqueued.
+void dense_gebal_run(Ctx *ctx, int dtype, int64_t n, void *A_dev, int64_t lda, int64_t *ilo, int64_t *ihi, double *scale_host, int64_t *sweeps);
 // phi!(out, A, k) of a device matrix (scaling and recovering, Taylor core): returns the slab [Phi_0 ... Phi_k] of packed n x n blocks in
 // the context's workspace and, with out_dev, enqueues the copies to out_dev[j] (leading dimension ldo).  A is only read.
 // info[0..2] = Taylor degree, scalings, products launched.  Synchronises the stream once (norm).

@@ -296,6 +296,29 @@ int expv_mi_gemv_block(expv_mi_ctx_t ctx, int dtype, int64_t nrows, int64_t ncol
  * microseconds, [4..7] 0. */
 int expv_mi_expm(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t info[8]);
 
+/* exponential!(A, ExpMethodHigham2005Base()) for a dense matrix on the device -- exp_baseexp.jl:112-161, the algorithm of
+ * expv_mi_host_expm: the finite check (on opnorm(A, 1) of the caller's matrix: errors and the untouched A as expv_mi_expm), then
+ * gebal job 'B' (permute, then scale by powers of two; see expv_mi_gebal), opnorm(A_bal, 1) with fp64 column sums, then exactly
+ * expv_mi_expm's order / s selection, Pade, LU and squarings on the balanced matrix, and unbalance folded into the copy into A.
+ * ONE deliberate difference to expv_mi_expm and exp_noalloc.jl:117: the norm that selects order and s is taken AFTER balancing, as
+ * in exp_baseexp.jl:127-129.  For A = D B D^-1 with a badly scaled D it sees |B|, not |A|: dozens of squarings fewer, and none of
+ * their rounding.  The reference has no such method for a GPU array (its balancing routines index scalars).  On a matrix that
+ * balancing leaves alone the result is expv_mi_expm's bit for bit.  Arguments, loc, errors, n = 0, n > 65535 and completion as
+ * expv_mi_expm; a scaling loop that has not settled after 128 sweeps answers EXPV_MI_UNSUPPORTED with A untouched.
+ * info (may be NULL): [0..3] as expv_mi_expm, [4] ilo, [5] ihi (1-based), [6] sweeps of the scaling loop (the last one changes
+ * nothing), [7] microseconds spent balancing and undoing it (with stream-ordered outputs: without the last pass). */
+int expv_mi_expm_balanced(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t info[8]);
+
+/* LAPACK.gebal!('B', A) for a dense matrix on the device (or a staged host matrix, loc = EXPV_MI_HOST): A, column-major n x n with
+ * leading dimension lda >= n, is balanced in place (rows n..lda-1 untouched).  xGEBAL job 'B', 2-norm variant, radix 2, factor
+ * 0.95, the decisions and their order those of the host routine (expv_mi_host_gebal); the row and column norms are summed in fp64
+ * for every element type, the guards sfmin / sfmax are those of the element type's real type, -0.0 counts as zero.  *ilo, *ihi:
+ * 1-based; scale_host (HOST memory, n doubles) in LAPACK's convention: the factors inside ilo..ihi, outside them 1 + the position
+ * each one was exchanged with.  Any of the three may be NULL.  n = 0: *ilo = 1, *ihi = 0.  A non-finite entry answers
+ * EXPV_MI_ARGUMENT_ERROR as LAPACK.gebal!'s chkfinite does, n > 65535 EXPV_MI_UNSUPPORTED; A is untouched then. */
+int expv_mi_gebal(expv_mi_ctx_t ctx, int dtype, int64_t n, void *A, int64_t lda, int loc, int64_t *ilo, int64_t *ihi,
+                  double *scale_host);
+
 /* phi!(out, A, k) for a dense matrix on the device -- phi.jl:159-257: out[j] <- phi_j(A), j = 0 .. k (phi_0 = exp).  A: column-major
  * n x n, leading dimension lda >= n, NOT modified; out: a HOST array of k + 1 pointers to column-major n x n matrices with leading
  * dimension ldo >= n.  loc applies to A and to every out[j] (EXPV_MI_DEVICE: device pointers; EXPV_MI_HOST: staged through HBM).  Rows
@@ -555,6 +578,10 @@ int expv_mi_host_rcm(int64_t n, const int32_t *rowptr, const int32_t *colind, in
  * changes (the reference reads A at call time, krylov_phiv.jl / arnoldi.jl mul!); no counterpart in the reference. */
 int expv_mi_host_wrapsum(const void *buf, uint64_t nbytes, uint64_t out[2]);
 int expv_mi_host_expm(int dtype, int n, void *A, int lda);
+/* The balancing step of expv_mi_host_expm on its own (xGEBAL job 'B'; needs no GPU): A (column-major, leading dimension lda) is
+ * balanced in place in its own element type; *ilo, *ihi 1-based, scale (n doubles) in LAPACK's convention.  Any of the three may
+ * be NULL.  Unlike expv_mi_gebal the norms are summed in the element type's real type. */
+int expv_mi_host_gebal(int dtype, int n, void *A, int lda, int64_t *ilo, int64_t *ihi, double *scale);
 /* Z*(exp.(t*lambda).*Z[1,:]) of SymTridiagonal(d, e)  (krylov_phiv.jl:227-228); out: n complex */
 int expv_mi_host_symtridiag_expcol(int n, const double *d, const double *e, double t_re, double t_im,
                                    double *out_c64);

@@ -214,6 +214,23 @@ end
 # (do_balancing is ignored, as exp.jl:56-58 ignores it for an AbstractGPUArray)
 ExponentialUtilities.exponential!(A::MIMatrix{T}, ::ExponentialUtilities.ExpMethodHigham2005, cache = nothing) where {T <: MIScalar} =
     ExponentialUtilities.exponential!(A)
+# exponential!(A, ExpMethodHigham2005Base()) (exp_baseexp.jl:112-161), which the reference defines for a StridedMatrix only: gebal
+# job 'B' on the device, the norm taken AFTER balancing, unbalance folded into the copy into A.  The method for badly scaled A.
+function ExponentialUtilities.exponential!(A::MIMatrix{T}, ::ExponentialUtilities.ExpMethodHigham2005Base, cache = nothing) where {T <: MIScalar}
+    n = LinearAlgebra.checksquare(A)
+    info = zeros(Int64, 8)      # Pade order, squarings, row exchanges, microseconds, ilo, ihi, sweeps, microseconds of balancing
+    check(ccall((:expv_mi_expm_balanced, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Int64, Cint, Ptr{Int64}),
+                ctx().h, dtype(T), n, A.ptr, ld(A), DEVICE, info), ctx().h)
+    A
+end
+# LAPACK.gebal!('B', A) for a matrix in HBM: A balanced in place; returns (ilo, ihi, scale) with scale::Vector{Float64} on the host
+function balance!(A::MIMatrix{T}) where {T <: MIScalar}
+    n = LinearAlgebra.checksquare(A)
+    ilo, ihi, scale = Ref{Int64}(1), Ref{Int64}(0), ones(Float64, n)
+    check(ccall((:expv_mi_gebal, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Int64, Cint, Ref{Int64}, Ref{Int64}, Ptr{Cdouble}),
+                ctx().h, dtype(T), n, A.ptr, ld(A), DEVICE, ilo, ihi, scale), ctx().h)
+    Int(ilo[]), Int(ihi[]), scale
+end
 function LinearAlgebra.mul!(C::MIMatrix{T}, A::MIMatrix{T}, B::MIMatrix{T}, α::Number, β::Number) where {T <: MIScalar}
     m, n, k = size(C, 1), size(C, 2), size(A, 2)
     (size(A, 1) == m && size(B, 1) == k && size(B, 2) == n) || throw(DimensionMismatch("mul!: C is $(size(C)), A is $(size(A)), B is $(size(B))"))
