@@ -60,16 +60,24 @@ def _check(code, ctx=None):
 # context and raw device memory
 # ---------------------------------------------------------------------------------------------
 class Context:
-    """One GPU + one HIP stream (expv_mi_ctx_create).  ``stream`` may be a torch.cuda.Stream."""
+    """One GPU + one HIP stream (expv_mi_ctx_create).  ``stream``: None -- the library creates a private non-blocking stream -- or a
+    stream of the caller's (a torch.cuda.Stream, or a hipStream_t as an integer) that the library launches on and never destroys.
+    The null / legacy stream (handle 0, e.g. torch.cuda.default_stream()) cannot be adopted: the C ABI reads a NULL handle as
+    "create a private stream", and the caller would believe the library ordered with a stream it is not on."""
 
 
     def __init__(self, device=None, stream=None, async_outputs=False):
+        sptr = None
+        if stream is not None:
+            handle = getattr(stream, "cuda_stream", stream)
+            if not handle:
+                raise ValueError("Context(stream=...): the null / legacy stream (handle 0, e.g. torch.cuda.default_stream()) cannot be "
+                                 "adopted -- the library would silently work on a stream of its own.  Pass a stream you created "
+                                 "(torch.cuda.Stream()), or stream=None for a private stream of the library's.")
+            sptr = C.c_void_p(int(handle))
         lib = L.load()
         if device is None:
             device = int(os.environ.get("LOCAL_RANK", "0"))
-        sptr = None
-        if stream is not None:
-            sptr = C.c_void_p(getattr(stream, "cuda_stream", stream))
         h = C.c_void_p()
         _check(lib.expv_mi_ctx_create(int(device), sptr, C.byref(h)))
         self._h = h

@@ -71,7 +71,11 @@ typedef enum { EXPV_MI_ORTHO_AUTO = 0, EXPV_MI_ORTHO_MGS = 1, EXPV_MI_ORTHO_LOWS
 
 /* ------------------------------------------------------------------ context ---------- */
 /* One context = one GPU + one HIP stream.  `stream` may be NULL (library creates its own) or an
- * existing hipStream_t (e.g. torch.cuda.Stream().cuda_stream) that the library launches on. */
+ * existing hipStream_t (e.g. torch.cuda.Stream().cuda_stream) that the library launches on and never destroys: calls stay behind
+ * what the caller queued on it before, device outputs are valid for what the caller queues on it afterwards.  NULL always means
+ * "a private stream", so the null / legacy stream (handle 0, e.g. torch.cuda.default_stream().cuda_stream) cannot be adopted --
+ * a host that wants the library on torch's stream creates one (torch.cuda.Stream()) and passes that; the Python front end raises
+ * ValueError for a handle of 0 instead of creating a private stream behind the caller's back. */
 int expv_mi_ctx_create(int device_id, void *stream, expv_mi_ctx_t *ctx);
 int expv_mi_ctx_destroy(expv_mi_ctx_t ctx);
 int expv_mi_ctx_sync(expv_mi_ctx_t ctx);

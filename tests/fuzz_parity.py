@@ -14,7 +14,12 @@ default_rng([seed, index, 1]), so that the cases the suite cites by (seed, index
 A THIRD generator, default_rng([seed, index, 2]), replaces m (1 .. 40 from the first) in a small share of the cases
 (BOUNDARY_M_SHARE) by a value either side of the single-pass and the two-kernel window (BOUNDARY_M: 31 .. 33, 63 .. 66) -- the
 compiled-in limits of csrc/kernels.h, tests/test_gpu_limits.py; every other draw of every case stays what it was.
-A case with options runs on a private context from a small cache keyed by the option set; spin_limit is not drawn (an expired wait
+A FOURTH generator, default_rng([seed, index, 3]), puts a small share of the cases (CALLER_STREAM_SHARE, scaled by FUZZ_OPTIONS like the
+second axis) on a context bound to ONE torch stream of the caller's, shared by all of them (include/expv_mi.h, expv_mi_ctx_create: "an
+existing hipStream_t ... that the library launches on"; tests/test_gpu_caller_stream.py has the fixed cases), combined with stream-ordered
+outputs where the case draws them:
+    FUZZ_CALLER_STREAM=1  replay: force what a failing case printed as "caller_stream" (0: never)
+A case with options or on the caller's stream runs on a private context from a small cache keyed by (option set, async outputs, stream); spin_limit is not drawn (an expired wait
 is a timing matter with its own subprocess test) and `resident` keeps to the sizes of test_resident_form_matches_stepwise_and_oracle.
 Test infrastructure (imports the oracle); not part of the product or of the measured path."""
 import json
@@ -37,6 +42,8 @@ _env = __import__("os").environ
 FUZZ_OPTIONS = float(_env.get("FUZZ_OPTIONS", "0.5"))
 FUZZ_OPTION_SET = _env.get("FUZZ_OPTION_SET", "")
 FUZZ_DEVICE_SPARSE = _env.get("FUZZ_DEVICE_SPARSE", "")
+FUZZ_CALLER_STREAM = _env.get("FUZZ_CALLER_STREAM", "")
+CALLER_STREAM_SHARE = 0.16      # x FUZZ_OPTIONS: 8 % of the cases at the default 0.5, none at 0
 OPTION_NAMES = [k for k in OPTION_SETS if k != "default"]
 
 
@@ -138,8 +145,9 @@ def _limited(f, seconds):
 
 
 _ACTX = []
-_OCTX = {}          # (option set, async outputs) -> private context; insertion-ordered, the oldest dropped beyond _OCTX_MAX
+_OCTX = {}          # (option set, async outputs, on the caller's stream) -> private context; insertion-ordered, the oldest dropped beyond _OCTX_MAX
 _OCTX_MAX = 4
+_STREAM = []        # the one torch stream the caller-stream contexts share
 
 
 def _async_ctx():
@@ -148,16 +156,34 @@ def _async_ctx():
     return _ACTX[0]
 
 
-def _option_ctx(oname, async_outputs=False):
-    """the private context of an option set (options set before any operator exists on it); None = the default context"""
-    if oname == "default":
+def _caller_stream():
+    if not _STREAM:
+        import torch
+        _STREAM.append(torch.cuda.Stream())
+    return _STREAM[0]
+
+
+def _option_ctx(oname, async_outputs=False, caller_stream=False):
+    """the private context of an option set (options set before any operator exists on it), on a stream of its own or on the shared
+    caller's stream; None = the default context"""
+    if oname == "default" and not caller_stream:
         return _async_ctx() if async_outputs else None
-    key = (oname, async_outputs)
+    key = (oname, async_outputs, caller_stream)
     if key not in _OCTX:
         while len(_OCTX) >= _OCTX_MAX:
             _OCTX.pop(next(iter(_OCTX)))
-        _OCTX[key] = context_with(eu, OPTION_SETS[oname], async_outputs=async_outputs)
+        kw = {"stream": _caller_stream()} if caller_stream else {}
+        _OCTX[key] = context_with(eu, OPTION_SETS[oname], async_outputs=async_outputs, **kw)
     return _OCTX[key]
+
+
+def _draw_caller_stream(seed, index):
+    """whether the case's context is bound to the shared caller's stream -- from a generator of its own: every other draw stays what it was"""
+    rng4 = np.random.default_rng([seed, index, 3])
+    on = bool(rng4.random() < CALLER_STREAM_SHARE * FUZZ_OPTIONS)
+    if FUZZ_CALLER_STREAM:
+        on = FUZZ_CALLER_STREAM not in ("0", "false", "no")
+    return on
 
 
 def _draw_second_axis(seed, index):
@@ -235,9 +261,12 @@ def one_case(seed, index, verbose=False):
     oname, dsp = _draw_second_axis(seed, index)
     if "resident" in OPTION_SETS[oname] and n not in RESIDENT_SIZES:
         oname = "default"
-    ctx = _option_ctx(oname)          # None: the default context, as before
+    on_stream = _draw_caller_stream(seed, index)
+    ctx = _option_ctx(oname, caller_stream=on_stream)          # None: the default context, as before
     if oname != "default":
         desc["options"] = oname
+    if on_stream:
+        desc["caller_stream"] = 1
     if verbose:
         print(desc, flush=True)
     tol = 3e-4 if single else 1e-10
@@ -510,7 +539,7 @@ def one_case(seed, index, verbose=False):
         import torch
         if n > 200000:
             return desc, 0.0, tol, {"skipped": "size"}
-        actx = _option_ctx(oname, async_outputs=True)
+        actx = _option_ctx(oname, async_outputs=True, caller_stream=on_stream)
         op = eu.MIOperator(A, actx)
         tdt = {"float32": torch.float32, "float64": torch.float64, "complex64": torch.complex64, "complex128": torch.complex128}[T.name]
         nb = int(rng.integers(1, 4))
@@ -661,6 +690,7 @@ def main():
     fails = 0
     worst = {}
     options_seen, paths_seen = {}, {}
+    on_caller_stream = 0
     import signal
 
     def on_alarm(sig, frm):
@@ -676,6 +706,7 @@ def main():
             desc, err, tol, extra = one_case(seed, index)
             key = (desc["call"], "32" if desc["T"] in ("float32", "complex64") else "64")
             options_seen[desc.get("options", "default")] = options_seen.get(desc.get("options", "default"), 0) + 1
+            on_caller_stream += int(desc.get("caller_stream", 0))
             for word in desc.get("path", ()):
                 paths_seen[word] = paths_seen.get(word, 0) + 1
             if "skipped" not in extra:
@@ -692,7 +723,7 @@ def main():
     import faulthandler
     faulthandler.dump_traceback_later(60, exit=True)      # (a hang while the interpreter tears down is reported, not waited for)
     print(json.dumps({"cases": index - start, "failures": fails, "seconds": round(time.time() - t0, 1), "seed": seed, "fuzz_options": FUZZ_OPTIONS,
-                      "options_seen": dict(sorted(options_seen.items())), "paths_seen": dict(sorted(paths_seen.items())),
+                      "caller_stream": on_caller_stream, "options_seen": dict(sorted(options_seen.items())), "paths_seen": dict(sorted(paths_seen.items())),
                       "worst_by_call": {"%s/%s" % k: v for k, v in sorted(worst.items())}}), flush=True)
     sys.exit(1 if fails else 0)
 

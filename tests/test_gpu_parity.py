@@ -872,6 +872,7 @@ def test_randomised_parity_hunt_short():
     env = dict(os.environ, FUZZ_LARGE="0.02", FUZZ_OPTIONS="0")      # (FUZZ_OPTIONS=0: the stream this test has always run, on the default context)
     env.pop("FUZZ_OPTION_SET", None)
     env.pop("FUZZ_DEVICE_SPARSE", None)
+    env.pop("FUZZ_CALLER_STREAM", None)
     p = subprocess.run([sys.executable, os.path.join(root, "tests", "fuzz_parity.py"), "6", "20260928"], cwd=root, capture_output=True, text=True,
                        timeout=600, env=env)
     last = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -892,6 +893,7 @@ def test_randomised_parity_hunt_short_with_context_options():
     env = dict(os.environ, FUZZ_LARGE="0.02", FUZZ_OPTIONS="1")
     env.pop("FUZZ_OPTION_SET", None)
     env.pop("FUZZ_DEVICE_SPARSE", None)
+    env.pop("FUZZ_CALLER_STREAM", None)
     p = subprocess.run([sys.executable, os.path.join(root, "tests", "fuzz_parity.py"), "6", "20260928"], cwd=root, capture_output=True, text=True,
                        timeout=600, env=env)
     last = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -900,6 +902,7 @@ def test_randomised_parity_hunt_short_with_context_options():
     assert "default" not in r["options_seen"] or r["options_seen"]["default"] < r["cases"] // 10, r["options_seen"]      # (default: only `resident` off its sizes)
     for word in ("pipeline", "overlapped", "wave", "patch", "two_kernel", "modular"):
         assert r["paths_seen"].get(word, 0) > 0, (word, r["paths_seen"])
+    assert r["caller_stream"] > 0, r      # (the fourth axis: cases on a context bound to the shared caller's stream)
 
 
 # ------------------------------------------------------------------ reordered operators (reorder.h) --------
