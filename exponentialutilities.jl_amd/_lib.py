@@ -87,6 +87,7 @@ PROTOTYPES = {
     "expv_mi_op_create_csr": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _i, _i, _pvp]),
     "expv_mi_op_create_csr_loc": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _pvp]),
     "expv_mi_op_create_csc_loc": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _pvp]),
+    "expv_mi_op_create_coo_loc": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _pvp]),
     "expv_mi_op_ingest_info": (_i, [_vp, _vp]),
     "expv_mi_op_create_dense": (_i, [_vp, _i, _i64, _vp, _i64, _i, _pvp]),
     "expv_mi_op_create_callback": (_i, [_vp, _i, _i64, MATVEC_FN, _vp, _i, _i64, _pvp]),

@@ -393,6 +393,55 @@ def _unpack_torch_sparse(A):
     return fmt, ptr.contiguous(), idx.contiguous(), vals.contiguous(), (int(A.shape[0]), int(A.shape[1]))
 
 
+def _is_torch_coo(A):
+    if not _is_torch_sparse(A):
+        return False
+    import torch
+    return A.layout == torch.sparse_coo
+
+
+def _unpack_torch_coo(A):
+    """The parts of a 2-D, square, non-hybrid ``torch.sparse_coo`` tensor, coalesced or not, on whatever device it lives:
+    ``(row, col, vals, shape)`` -- the two rows of ``A._indices()`` (the public accessors refuse uncoalesced tensors) and
+    ``A._values()``, contiguous, without a copy of anything that is contiguous already; nothing moves between devices."""
+    import torch
+    if A.layout != torch.sparse_coo:
+        raise TypeError(f"not a torch.sparse_coo tensor: {A.layout}")
+    if A.dense_dim() != 0:
+        raise DimensionMismatch("a sparse operator has scalar entries (no dense dimensions)")
+    if A.dim() != 2 or A.sparse_dim() != 2:
+        raise DimensionMismatch("a sparse operator is one 2-D matrix (no batch dimensions)")
+    if A.shape[0] != A.shape[1]:
+        raise DimensionMismatch("operator must be square")
+    ind, vals = A._indices(), A._values()
+    if vals.dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
+        raise TypeError(f"sparse operator values must be float32 / float64 / complex64 / complex128, not {vals.dtype}")
+    return ind[0].contiguous(), ind[1].contiguous(), vals.contiguous(), (int(A.shape[0]), int(A.shape[1]))
+
+
+def _coo_index_arrays(row, col):
+    """the two index arrays of a triplet list as the library takes them: both int32 or both int64, contiguous, 1-D, where they lie"""
+    if _is_torch(row) != _is_torch(col):
+        raise TypeError("from_coo: row and col must both be torch tensors or both be arrays")
+    if _is_torch(row):
+        import torch
+        if row.device != col.device:
+            raise ValueError("from_coo: row and col live on different devices")
+        if row.dtype != col.dtype or row.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"sparse operator indices must be int32 or int64, not {row.dtype} / {col.dtype}")
+        row, col = row.contiguous(), col.contiguous()
+        if not row.is_cuda:
+            row, col = row.numpy(), col.numpy()
+    else:
+        row, col = np.asarray(row), np.asarray(col)
+        if row.dtype != col.dtype or row.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise TypeError(f"sparse operator indices must be int32 or int64, not {row.dtype} / {col.dtype}")
+        row, col = np.ascontiguousarray(row), np.ascontiguousarray(col)
+    if row.ndim != 1 or col.ndim != 1 or row.shape[0] != col.shape[0]:
+        raise DimensionMismatch("from_coo: row and col must be vectors of one length")
+    return row, col
+
+
 def _torch_sparse_to_scipy(A):
     """a CPU torch.sparse_csr / sparse_csc tensor as the scipy matrix of the same format (shares the arrays)"""
     import scipy.sparse as sp
@@ -411,23 +460,32 @@ def _torch_ready(*tensors):
 
 class MIOperator:
     """Device-resident operator: scipy CSC/CSR matrix, ``torch.sparse_csr`` / ``torch.sparse_csc`` tensor, dense ndarray or
-    tensor, or a matrix-free callable.
+    tensor, or a matrix-free callable; coordinate triplets through ``from_coo``.
 
     ``MIOperator(A)`` uploads once (CSC is converted to CSR32 on the way; setup cost).  A sparse tensor that lives on the GPU is
     taken where it is (expv_mi_op_create_csr_loc / _csc_loc): its index arrays are checked on the device, only the pattern visits
-    the host (``ingest_info``), the values never do.  Exposes ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian),
+    the host (``ingest_info``), the values never do.  Coordinate triplets are handed over by name:
+    ``MIOperator.from_coo(A)`` for a ``torch.sparse_coo`` tensor (coalesced or not, on either side; ``expv(t, A, b)`` and the
+    other front ends take such a tensor as ``A`` directly) and ``MIOperator.from_coo(row, col, vals, n)`` for arrays; repeated
+    coordinates are added in entry order (expv_mi_op_create_coo_loc).  ``MIOperator(A)`` itself keeps refusing the layout.  A scipy ``coo_matrix`` keeps going through ``.tocsr()``, whose sum has scipy's order --
+    ``from_coo`` is the way to the entry-order sum.  Exposes ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian),
     ``nnz`` and ``opnorm_inf``.
     """
 
-    def __init__(self, A, ctx=None, dtype=None, ishermitian=None, matvec=None, shape=None, matvec_c=None):
+    def __init__(self, A, ctx=None, dtype=None, ishermitian=None, matvec=None, shape=None, matvec_c=None, _coo=None):
         lib = L.load()
         self.ctx = ctx or default_context()
+        if _is_torch_coo(A):                           # triplets are handed over by name: the constructor stays with compressed layouts
+            raise TypeError("MIOperator(A) takes sparse torch tensors of layout torch.sparse_csr or torch.sparse_csc; a "
+                            f"{A.layout} tensor holds coordinate triplets: MIOperator.from_coo(A), or pass it to expv / phiv / ... as A")
         if _is_torch_sparse(A) and not A.is_cuda:      # a host matrix in torch's clothes: the scipy path
             A = _torch_sparse_to_scipy(A)
         self.src = A
         h = C.c_void_p()
         self._cb = None
-        if matvec_c is not None:        # matrix-free, compiled: (function pointer of type expv_mi_matvec_fn, user pointer) -- what a Julia
+        if _coo is not None:
+            dt = self._create_coo(lib, h, *_coo, dtype=dtype)
+        elif matvec_c is not None:        # matrix-free, compiled: (function pointer of type expv_mi_matvec_fn, user pointer) -- what a Julia
             fn, user = matvec_c         # host passes as a @cfunction; nothing of Python runs inside the factorisation
             n = int(shape[0])
             dt = np.dtype(dtype or np.float64)
@@ -534,7 +592,9 @@ class MIOperator:
         self._h = h
         self._finalizer = weakref.finalize(self, lib.expv_mi_op_destroy, h)
         try:            # element type the caller handed over (Float32 operands: see _ref_dtype)
-            if A is None:
+            if _coo is not None:
+                self.src_dtype = _np_dtype_of(_coo[2]) if _is_torch(_coo[2]) else np.dtype(np.asarray(_coo[2]).dtype)
+            elif A is None:
                 self.src_dtype = np.dtype(dtype or np.float64)
             elif hasattr(A, "indptr") or isinstance(A, np.ndarray):
                 self.src_dtype = np.dtype(A.dtype)
@@ -551,6 +611,56 @@ class MIOperator:
         self.ishermitian = bool(herm.value) if ishermitian is None else bool(ishermitian)
         self.opnorm_inf = float(opn.value)
         self.dtype = np.dtype({L.F64: np.float64, L.C64: np.complex128, L.F32: np.float32, L.C32: np.complex64}[dtc.value])
+
+    @classmethod
+    def from_coo(cls, row, col=None, vals=None, n=None, index_base=0, ctx=None, dtype=None):
+        """``from_coo(A)``: the operator of a 2-D, square ``torch.sparse_coo`` tensor, coalesced or not, on the GPU or the CPU
+        (read through ``A._indices()`` / ``A._values()``, no copy of what is contiguous).  ``from_coo(row, col, vals, n)``:
+        the n x n operator of the coordinate triplets ``(row[k], col[k], vals[k])`` (expv_mi_op_create_coo_loc): numpy arrays
+        or torch tensors, indices int32 or int64 with the given base, in any order, repeats allowed.  Entries of one coordinate
+        are ADDED, in the operator's element type and in ascending order of k -- Julia's ``sparse(I, J, V, n, n)``, with the
+        order of the sum fixed -- and a sum that comes out as zero stays stored.  Tensors on the GPU are taken where they are
+        (checked, sorted and compressed on the device; the values never visit the host); host arrays are staged and take the same
+        path, so both give the same bits.  ``update_values`` then takes one value per triplet, in triplet order."""
+        if _is_torch_coo(row):
+            if col is not None or vals is not None:
+                raise TypeError("from_coo: either one torch.sparse_coo tensor or row, col, vals, n")
+            row, col, vals, shp = _unpack_torch_coo(row)
+            if n is not None and int(n) != shp[0]:
+                raise DimensionMismatch("from_coo: n differs from the tensor's shape")
+            n, index_base = shp[0], 0
+        elif col is None or vals is None or n is None:
+            raise TypeError("from_coo: row, col, vals and n are required")
+        return cls(None, ctx, dtype=dtype, _coo=(row, col, vals, int(n), int(index_base)))
+
+    def _create_coo(self, lib, h, row, col, vals, n, index_base, dtype=None):
+        row, col = _coo_index_arrays(row, col)
+        on_dev = _is_torch(row)
+        dt = _work_dtype((_np_dtype_of(vals) if _is_torch(vals) else np.asarray(vals).dtype) if dtype is None else dtype)
+        if on_dev:
+            import torch
+            if row.device.index not in (None, self.ctx.device):
+                raise ValueError(f"triplets live on {row.device}, the context on device {self.ctx.device}")
+            vals = torch.as_tensor(vals, device=row.device)
+            if vals.dtype != _torch_dtype(dt):
+                vals = vals.to(_torch_dtype(dt))      # (on the device)
+            vals = vals.contiguous()
+            _torch_ready(row, col, vals)
+            ptrs, nent = (row.data_ptr(), col.data_ptr(), vals.data_ptr()), int(row.numel())
+            isz, nval, loc = row.element_size(), int(vals.numel()), L.DEVICE
+        else:
+            if _is_torch(vals):
+                vals = vals.cpu().numpy()
+            vals = np.ascontiguousarray(vals, dtype=dt)
+            ptrs, nent = (row.ctypes.data, col.ctypes.data, vals.ctypes.data), int(row.shape[0])
+            isz, nval, loc = row.dtype.itemsize, int(vals.size), L.HOST
+        if vals.ndim != 1 or nval != nent:
+            raise DimensionMismatch("from_coo: one value per (row, col) pair expected")
+        self._sp_format, self._sp_sorted = "coo", True
+        self._coo_parts = (row, col, vals, int(n), int(index_base))      # update_values compares, astype rebuilds
+        _check(lib.expv_mi_op_create_coo_loc(self.ctx._h, _code(dt), int(n), nent, ptrs[0] if nent else None, ptrs[1] if nent else None,
+                                             ptrs[2] if nent else None, isz, int(index_base), loc, C.byref(h)), self.ctx._h)
+        return dt
 
     @property
     def reorder_info(self):
@@ -574,11 +684,13 @@ class MIOperator:
     def ingest_info(self):
         """How a sparse operator came to be (expv_mi_op_ingest_info): ``from_device`` -- created from arrays on the device --,
         the bytes of pattern and of values that were brought to the host for it (values: 0 unless a row is unsorted or holds a
-        duplicate), the creation time and the share of the device checks, and whether the ordering plan came from the plan cache."""
+        duplicate), the creation time and the share of the device checks, whether the ordering plan came from the plan cache, and
+        for an operator made from triplets ``coo_entries`` -- how many were handed over -- and the ``sort_passes`` that ran."""
         out = (C.c_int64 * 8)()
         _check(L.load().expv_mi_op_ingest_info(self._h, out))
         return {"from_device": bool(out[0]), "pattern_bytes_to_host": int(out[1]), "value_bytes_to_host": int(out[2]),
-                "create_s": 1e-6 * int(out[3]), "ingest_s": 1e-6 * int(out[4]), "plan_cached": bool(out[5])}
+                "create_s": 1e-6 * int(out[3]), "ingest_s": 1e-6 * int(out[4]), "plan_cached": bool(out[5]),
+                "coo_entries": int(out[6]), "sort_passes": int(out[7])}
 
     def update_values(self, A):
         """New values on the same sparsity pattern (expv_mi_op_update_values): ``A`` is the matrix the operator was created
@@ -588,6 +700,8 @@ class MIOperator:
         fmt = getattr(self, "_sp_format", None)
         if fmt is None:
             raise ValueError("update_values: sparse operators only")
+        if fmt == "coo":
+            return self._update_coo(A)
         if _is_torch_sparse(A):
             if not hasattr(self, "_dev_parts"):
                 raise ValueError("update_values: a sparse tensor refreshes an operator that was created from one")
@@ -622,10 +736,48 @@ class MIOperator:
             delattr(self, key)
         return self
 
+    def _update_coo(self, A):
+        """update_values of an operator made from triplets: one value per triplet in triplet order (an array, a tensor, or a
+        torch.sparse_coo tensor with the indices of the creation); summed as at creation, bit-equal to creating anew"""
+        row, col, old, n, base = self._coo_parts
+        nent = int(row.shape[0])
+        if _is_torch_coo(A):
+            r2, c2, vals, shp = _unpack_torch_coo(A)
+            same = shp == self.shape and int(r2.shape[0]) == nent and _is_torch(row) == r2.is_cuda
+            if same and _is_torch(row):
+                import torch
+                same = r2.dtype == row.dtype and bool(torch.equal(r2, row)) and bool(torch.equal(c2, col))
+            elif same:
+                same = np.array_equal(r2.numpy() - 0, row - base) and np.array_equal(c2.numpy() - 0, col - base)
+            if not same:
+                raise ValueError("update_values: a sparse_coo tensor with the shape and the indices of the creation required")
+        else:
+            vals = A
+        if _is_torch(vals) and not vals.is_cuda:
+            vals = vals.numpy()
+        arg = _Arg(vals if _is_torch(vals) else np.ascontiguousarray(vals, dtype=self.dtype), self.dtype)
+        if len(arg.shape) != 1 or int(arg.shape[0]) != nent:
+            raise DimensionMismatch("update_values: one value per triplet of the creation expected (%d)" % nent)
+        _check(L.load().expv_mi_op_update_values(self._h, arg.ptr, arg.loc), self.ctx._h)
+        self._coo_parts = (row, col, arg.keep, n, base)
+        n_, nnz, herm, opn, dtc = C.c_int64(), C.c_int64(), C.c_int(), C.c_double(), C.c_int()
+        _check(L.load().expv_mi_op_info(self._h, C.byref(n_), C.byref(nnz), C.byref(herm), C.byref(opn), C.byref(dtc)))
+        self.ishermitian = bool(herm.value)
+        self.opnorm_inf = float(opn.value)
+        for key in [k for k in vars(self) if k.startswith("_as_")]:      # converted copies hold the old values
+            delattr(self, key)
+        return self
+
     def astype(self, dtype):
         dtype = _work_dtype(dtype)
         if dtype == self.dtype:
             return self
+        if getattr(self, "_sp_format", None) == "coo":      # rebuilt from the kept triplets (on the device when they are there)
+            key = "_as_" + dtype.name
+            if not hasattr(self, key):
+                row, col, vals, n, base = self._coo_parts
+                setattr(self, key, MIOperator.from_coo(row, col, vals, n, base, self.ctx, dtype=dtype))
+            return getattr(self, key)
         if self.src is None or self._cb is not None:
             raise TypeError("cannot convert a matrix-free operator to another element type")
         key = "_as_" + dtype.name
@@ -694,6 +846,8 @@ def _as_operator(A, want_dtype=None, ctx=None):
         A = A.tocsr()
     if isinstance(A, MIOperator):
         op = A
+    elif _is_torch_coo(A):          # coordinate triplets, coalesced or not, on either side (MIOperator.from_coo)
+        op = MIOperator.from_coo(A, ctx=ctx)
     elif _is_torch(A):
         op = MIOperator(A, ctx)
     else:

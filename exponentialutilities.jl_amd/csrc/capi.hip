@@ -1662,9 +1662,51 @@ int expv_mi_op_create_csr(expv_mi_ctx_t ctx, int dtype, int64_t n, const void *r
 
 // ---- sparse operators from arrays that live on the device ------------------------------------------------------------------------
 namespace {
+// The tail every device-born sparse operator shares, from a clean status record on: ptr32 / idx32 are the checked, zero-based
+// device arrays (CSR32, or CSC32 for a CSC caller), `vals` the device values in the order of idx32.  Only the PATTERN comes to the
+// host (4 (n + 1 + nnz) bytes: the planners live here); `extra` dresses the operator with what its creator keeps on it.
+void finish_sparse_device(Ctx *ctx, const std::string &who, bool csc, int dtype, int64_t n, int64_t nnz, DevBuf &ptr32, DevBuf &idx32,
+                          const void *vals, bool caller_sorted, std::chrono::steady_clock::time_point t_begin, int64_t ingest_us, const std::function<void(Op &)> &extra,
+                          expv_mi_op_t *out) {
+  hipStream_t s = ctx->stream;
+  std::unique_ptr<expv_mi_op_s> op(new expv_mi_op_s());
+  op->ctx = ctx;
+  op->device = ctx->device;
+  op->dtype = dtype;
+  std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
+  HIPCHECK(hipMemcpyAsync(rp.data(), ptr32.p, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, s));
+  if (nnz > 0) HIPCHECK(hipMemcpyAsync(ci.data(), idx32.p, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  op->ingest[0] = 1;
+  op->ingest[1] = (int64_t)(sizeof(int32_t) * (rp.size() + ci.size()));
+  if (csc) {      // columns -> rows, on the pattern; the device copies are of the caller's columns: not what is stored
+    std::vector<int32_t> rp2, ci2;
+    csc_to_csr_pattern<int32_t>(n, rp.data(), ci.data(), 0, rp2, ci2, op->csc_pos);
+    rp.swap(rp2);
+    ci.swap(ci2);
+    ptr32.release();
+    idx32.release();
+  }
+  dispatch_host_dtype(dtype, [&](auto tag) {
+    using V = typename decltype(tag)::type;
+    make_csr_op_device<V>(*op, n, rp, ci, ptr32, idx32, vals);
+  });
+  // every row strictly ascending, as counted on the device: what the host analysis of the stored pattern must find too for an
+  // operator that keeps its creator's order (a CSC caller's rows are made here, sorted by construction)
+  if (!csc && !op->perm && op->rows_sorted_unique != caller_sorted)
+    fail(EXPV_MI_ASSERTION, who + ": device and host disagree on whether the rows are sorted and free of duplicates");
+  extra(*op);
+  const auto t_end = std::chrono::steady_clock::now();
+  op->ingest[3] = (int64_t)std::chrono::duration<double, std::micro>(t_end - t_begin).count();
+  op->ingest[4] = ingest_us;
+  op->ingest[5] = op->plan_cached ? 1 : 0;
+  ctx->adopt(&op->ctx);
+  *out = op.release();
+}
+
 // One body for CSR and CSC callers.  The caller's index arrays are checked and normalised by the ingest kernels (op_ingest.hip)
 // before anything -- on the device or here -- indexes by them; a violated condition is reported in the host creators' words and
-// nothing else has run.  Then only the normalised PATTERN comes to the host (4 (n + 1 + nnz) bytes: the planners live here).
+// nothing else has run.
 void create_sparse_device(Ctx *ctx, bool csc, int dtype, int64_t n, int64_t nnz, const void *ptr, const void *idx, const void *vals,
                           int idx_bytes, int index_base, expv_mi_op_t *out) {
   const std::string who = csc ? "op_create_csc" : "op_create_csr";
@@ -1691,39 +1733,111 @@ void create_sparse_device(Ctx *ctx, bool csc, int dtype, int64_t n, int64_t nnz,
   if (st.flags & dev::INGEST_BAD_NNZ) fail(EXPV_MI_ARGUMENT_ERROR, who + ": nnz must equal " + pname + "[n] - index base");
   if (st.flags & dev::INGEST_BAD_INDEX)
     fail(EXPV_MI_ARGUMENT_ERROR, (csc ? std::string("sparse operator: row index out of range") : who + ": column index out of range") + at(st.first_idx));
-  std::unique_ptr<expv_mi_op_s> op(new expv_mi_op_s());
-  op->ctx = ctx;
-  op->device = ctx->device;
-  op->dtype = dtype;
-  std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
-  HIPCHECK(hipMemcpyAsync(rp.data(), ptr32.p, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, s));
-  if (nnz > 0) HIPCHECK(hipMemcpyAsync(ci.data(), idx32.p, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  op->ingest[0] = 1;
-  op->ingest[1] = (int64_t)(sizeof(int32_t) * (rp.size() + ci.size()));
-  // every row strictly ascending, as counted on the device: what the host analysis of the stored pattern must find too for an
-  // operator that keeps a CSR caller's order (checked below; a CSC caller's rows are made here, sorted by construction)
-  const bool caller_sorted = st.desc_all == st.desc_starts;
-  if (csc) {      // columns -> rows, on the pattern; the device copies are of the caller's columns: not what is stored
-    std::vector<int32_t> rp2, ci2;
-    csc_to_csr_pattern<int32_t>(n, rp.data(), ci.data(), 0, rp2, ci2, op->csc_pos);
-    rp.swap(rp2);
-    ci.swap(ci2);
-    ptr32.release();
-    idx32.release();
+  finish_sparse_device(ctx, who, csc, dtype, n, nnz, ptr32, idx32, vals, st.desc_all == st.desc_starts, t_begin,
+                       (int64_t)std::chrono::duration<double, std::micro>(t_ingest - t_begin).count(), [](Op &) {}, out);
+}
+
+// Coordinate triplets -> the checked CSR32 arrays (op_coo.hip), then the same tail.  loc = HOST stages the three arrays into HBM
+// and takes the same path: one implementation, the same bits.
+void create_coo_device(Ctx *ctx, int dtype, int64_t n, int64_t nnz, const void *row, const void *col, const void *vals, int idx_bytes,
+                       int index_base, int loc, expv_mi_op_t *out) {
+  const std::string who = "op_create_coo";
+  const auto t_begin = std::chrono::steady_clock::now();
+  if (!out) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null output");
+  if (idx_bytes != 4 && idx_bytes != 8) fail(EXPV_MI_ARGUMENT_ERROR, who + ": idx_bytes must be 4 or 8");
+  if (n < 0 || n > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, who + ": n out of range for CSR32");
+  check_device_dtype(dtype, who.c_str());
+  if (nnz < 0) fail(EXPV_MI_ARGUMENT_ERROR, who + ": negative nnz");
+  if (nnz > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, who + ": nnz exceeds CSR32");
+  if (nnz > 0 && (!row || !col || !vals)) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null row / col / vals");
+  hipStream_t s = ctx->stream;
+  const size_t vbytes = dtype == EXPV_MI_C64 ? 16 : dtype == EXPV_MI_F32 ? 4 : 8;
+  DevBuf srow, scol, sval;
+  if (loc == EXPV_MI_HOST && nnz > 0) {
+    srow.alloc((size_t)idx_bytes * nnz);
+    scol.alloc((size_t)idx_bytes * nnz);
+    sval.alloc(vbytes * nnz);
+    HIPCHECK(hipMemcpyAsync(srow.p, row, srow.bytes, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(scol.p, col, scol.bytes, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(sval.p, vals, sval.bytes, hipMemcpyHostToDevice, s));
+    row = srow.p;
+    col = scol.p;
+    vals = sval.p;
   }
-  dispatch_host_dtype(dtype, [&](auto tag) {
-    using V = typename decltype(tag)::type;
-    make_csr_op_device<V>(*op, n, rp, ci, ptr32, idx32, vals);
-  });
-  if (!csc && !op->perm && op->rows_sorted_unique != caller_sorted)
-    fail(EXPV_MI_ASSERTION, who + ": device and host disagree on whether the rows are sorted and free of duplicates");
-  const auto t_end = std::chrono::steady_clock::now();
-  op->ingest[3] = (int64_t)std::chrono::duration<double, std::micro>(t_end - t_begin).count();
-  op->ingest[4] = (int64_t)std::chrono::duration<double, std::micro>(t_ingest - t_begin).count();
-  op->ingest[5] = op->plan_cached ? 1 : 0;
-  ctx->adopt(&op->ctx);
-  *out = op.release();
+  // events around the device stage: what expv_mi_op_ingest_info reports as out[4] (kernels + the two status read-backs)
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HIPCHECK(hipEventCreate(&ev0));
+  HIPCHECK(hipEventCreate(&ev1));
+  struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev_guard{ev0, ev1};
+  HIPCHECK(hipEventRecord(ev0, s));
+  DevBuf key[2], pay[2], hist, part, st_dev(sizeof(dev::CooStatus));
+  key[0].alloc(sizeof(unsigned long long) * (size_t)std::max<int64_t>(nnz, 1) + 16);
+  dev::coo_keys(s, idx_bytes, row, col, n, nnz, index_base, key[0].as<unsigned long long>(), st_dev.as<dev::CooStatus>());
+  dev::CooStatus st;
+  HIPCHECK(hipMemcpyAsync(&st, st_dev.p, sizeof(st), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  auto at = [](unsigned long long pos) { return " (first at position " + std::to_string(pos) + ")"; };
+  if (st.flags & dev::COO_BAD_ROW) fail(EXPV_MI_ARGUMENT_ERROR, who + ": row index out of range" + at(st.first_row));
+  if (st.flags & dev::COO_BAD_COL) fail(EXPV_MI_ARGUMENT_ERROR, who + ": column index out of range" + at(st.first_col));
+  // from here on every index is in [0, n)
+  const bool need_sort = st.descents > 0, need_sum = need_sort || st.repeats > 0;
+  int passes = 0;
+  if (need_sort) {
+    key[1].alloc(key[0].bytes);
+    pay[0].alloc(sizeof(int32_t) * (size_t)nnz);
+    pay[1].alloc(sizeof(int32_t) * (size_t)nnz);
+    hist.alloc(sizeof(uint32_t) * (size_t)dev::coo_hist_words(nnz));
+    unsigned long long *kp[2] = {key[0].as<unsigned long long>(), key[1].as<unsigned long long>()};
+    int32_t *pp[2] = {pay[0].as<int32_t>(), pay[1].as<int32_t>()};
+    passes = dev::coo_sort(s, n, nnz, kp, pp, hist.as<uint32_t>());
+  }
+  DevBuf &skey = key[passes & 1], &src = pay[passes & 1];
+  int64_t stored = 0;
+  DevBuf ptr32(sizeof(int32_t) * (size_t)(n + 1));
+  if (nnz > 0) {
+    part.alloc(sizeof(uint32_t) * (size_t)dev::coo_scan_words(nnz));
+    dev::coo_count_heads(s, skey.as<unsigned long long>(), nnz, part.as<uint32_t>(), st_dev.as<dev::CooStatus>());
+    unsigned long long cnt = 0;
+    HIPCHECK(hipMemcpyAsync(&cnt, &st_dev.as<dev::CooStatus>()->stored, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    stored = (int64_t)cnt;
+    if (stored < 1 || stored > nnz) fail(EXPV_MI_ASSERTION, who + ": bad count of distinct coordinates");
+  }
+  DevBuf idx32(sizeof(int32_t) * (size_t)std::max<int64_t>(stored, 1) + 16), seg(sizeof(int32_t) * (size_t)(stored + 1)), summed;
+  if (nnz > 0) {
+    dev::coo_compress(s, skey.as<unsigned long long>(), n, nnz, stored, part.as<uint32_t>(), ptr32.as<int32_t>(), idx32.as<int32_t>(), seg.as<int32_t>());
+    if (need_sum) {
+      summed.alloc(vbytes * (size_t)stored);
+      dispatch_host_dtype(dtype, [&](auto tag) {
+        using T = typename DevOf<typename decltype(tag)::type>::type;
+        dev::coo_segment_sums<T>(s, reinterpret_cast<const T *>(vals), need_sort ? src.as<int32_t>() : nullptr, seg.as<int32_t>(), stored, summed.as<T>());
+      });
+      vals = summed.p;
+    }
+  } else {
+    HIPCHECK(hipMemsetAsync(ptr32.p, 0, ptr32.bytes, s));
+  }
+  HIPCHECK(hipEventRecord(ev1, s));
+  HIPCHECK(hipEventSynchronize(ev1));
+  float ms = 0.0f;
+  HIPCHECK(hipEventElapsedTime(&ms, ev0, ev1));
+  key[0].release();
+  key[1].release();
+  pay[(passes & 1) ^ 1].release();
+  hist.release();
+  part.release();
+  finish_sparse_device(ctx, who, false, dtype, n, stored, ptr32, idx32, vals, true, t_begin, (int64_t)(1e3 * ms),
+                       [&](Op &op) {
+                         op.coo_entries = nnz;
+                         op.ingest[6] = nnz;
+                         op.ingest[7] = passes;
+                         if (need_sum) {      // what a triplet-ordered value refresh needs
+                           op.coo_map = true;
+                           if (need_sort) op.coo_src = std::move(src);
+                           op.coo_seg = std::move(seg);
+                         }
+                       },
+                       out);
 }
 }  // namespace
 
@@ -1771,6 +1885,16 @@ int expv_mi_op_create_csc_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t n
     if (loc != EXPV_MI_DEVICE) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_csc: bad location");
     ctx->use();
     create_sparse_device(ctx, true, dtype, n, nnz, colptr, rowval, nzval, idx_bytes, index_base, out);
+  });
+}
+
+int expv_mi_op_create_coo_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnz, const void *row, const void *col, const void *vals,
+                              int idx_bytes, int index_base, int loc, expv_mi_op_t *out) {
+  return guarded(ctx, [&] {
+    if (!ctx) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_coo: null context");
+    if (loc != EXPV_MI_DEVICE && loc != EXPV_MI_HOST) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_coo: bad location");
+    ctx->use();
+    create_coo_device(ctx, dtype, n, nnz, row, col, vals, idx_bytes, index_base, loc, out);
   });
 }
 
@@ -1930,7 +2054,22 @@ int expv_mi_op_update_values(expv_mi_op_t op, const void *vals, int loc) {
     if (op->nnz == 0) return;
     dispatch_host_dtype(op->dtype, [&](auto tag) {
       using V = typename decltype(tag)::type;
-      op_update_values_T<typename DevOf<V>::type, V>(*op, vals, loc);
+      using T = typename DevOf<V>::type;
+      if (op->coo_map) {      // triplet-born: the caller's coo_entries values, summed exactly as at creation, then the common refill
+        hipStream_t s = op->ctx->stream;
+        const void *v = vals;
+        if (loc == EXPV_MI_HOST) {
+          const size_t need = sizeof(T) * (size_t)op->coo_entries;
+          if (op->upd_stage.bytes < need) op->upd_stage.alloc(need + 16);
+          HIPCHECK(hipMemcpyAsync(op->upd_stage.p, vals, need, hipMemcpyHostToDevice, s));
+          v = op->upd_stage.p;
+        }
+        if (!op->coo_sum.p) op->coo_sum.alloc(sizeof(T) * (size_t)op->nnz);
+        dev::coo_segment_sums<T>(s, reinterpret_cast<const T *>(v), op->coo_src.as<int32_t>(), op->coo_seg.as<int32_t>(), op->nnz, op->coo_sum.as<T>());
+        op_update_values_T<T, V>(*op, op->coo_sum.p, EXPV_MI_DEVICE);
+      } else {
+        op_update_values_T<T, V>(*op, vals, loc);
+      }
     });
   });
 }

@@ -314,7 +314,14 @@ struct Op {
   int64_t ring_col_unique = 0;      // SELL column blocks kept after sharing equal ones (slices)
   // how the operator came to be (expv_mi_op_ingest_info): [0] 1 = from device arrays, [1] pattern bytes / [2] value bytes brought to the
   // host, [3] whole creation / [4] ingest kernels + status read-back in microseconds, [5] 1 = plan from the plan cache
+  // [6] entries of the coordinate triplets the operator was created from (0: CSR / CSC born), [7] sort passes that ran for them
   int64_t ingest[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // triplet-born (capi.hip: create_coo_device): entries handed over; when a coordinate repeated or the entries had to be sorted,
+  // the map a triplet-ordered value refresh sums through -- coo_src[p] = caller position of sorted position p (null: the identity),
+  // coo_seg[e] .. coo_seg[e + 1] - 1 = sorted positions of stored entry e -- and the buffer the sums go to
+  int64_t coo_entries = 0;
+  bool coo_map = false;
+  DevBuf coo_src, coo_seg, coo_sum;
   bool plan_cached = false;      // the ordering / patch plan came from the process-wide plan cache (capi.hip: OrderPlanCache)
   int64_t ring_sum = 0, ring_over128 = 0, ring_tiles = 0;      // sum of the ring lengths, tiles with a ring of more than 128 rows, tiles
   int ring_pad = 0;          // 0: no patch form

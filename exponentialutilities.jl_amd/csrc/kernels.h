@@ -98,6 +98,35 @@ struct IngestStatus {          // device words, read back once
 // (idx32 16-byte aligned) + the status record.  No access is indexed by an unchecked value.
 void ingest_indices(hipStream_t s, int idx_bytes, const void *ptr, const void *idx, int64_t n, int64_t nnz, int base, int32_t *ptr32,
                     int32_t *idx32, IngestStatus *st);
+// ---- a caller's coordinate triplets on the device: checked, sorted, coalesced, compressed there (op_coo.hip; capi.hip: create_coo_device) ----
+enum : unsigned long long {
+  COO_BAD_ROW = 1,           // a row index outside [0, n)
+  COO_BAD_COL = 2            // a column index outside [0, n)
+};
+struct CooStatus {             // device words; read back once after coo_keys, `stored` alone after coo_count_heads
+  unsigned long long flags;
+  unsigned long long first_row, first_col;      // first offending position in row / col (~0: none)
+  unsigned long long descents, repeats;         // positions k >= 1 with key[k] < key[k - 1] / key[k] == key[k - 1]
+  unsigned long long stored;                    // distinct coordinates
+  unsigned long long pad[2];
+};
+int coo_tile();                                  // entries a workgroup takes per sort pass (COO_TILE)
+int64_t coo_hist_words(int64_t nnz);             // 32-bit words of the sort's digit table + scan partials
+int64_t coo_scan_words(int64_t nnz);             // 32-bit words of the head scan's partials
+// row[nnz], col[nnz] (idx_bytes 4 or 8, index base `base`; 8-byte aligned at least) -> key[k] = row << 32 | col, zero-based
+// (key 16-byte aligned) + the status record.  Indexes by positions only.
+void coo_keys(hipStream_t s, int idx_bytes, const void *row, const void *col, int64_t n, int64_t nnz, int base, unsigned long long *key,
+              CooStatus *st);
+// stable sort of key[0][0 .. nnz) with the entry positions as payload; returns the passes p that ran: the result is in
+// key[p & 1] / pay[p & 1] (p == 0: n <= 1, nothing to order, no payload written)
+int coo_sort(hipStream_t s, int64_t n, int64_t nnz, unsigned long long *key[2], int32_t *pay[2], uint32_t *hist);
+// sorted keys -> st->stored = distinct keys, `part` = what coo_compress continues from
+void coo_count_heads(hipStream_t s, const unsigned long long *key, int64_t nnz, uint32_t *part, CooStatus *st);
+// ... -> rowptr[n + 1], colind[nstored] (16-byte aligned), seg[nstored + 1]
+void coo_compress(hipStream_t s, const unsigned long long *key, int64_t n, int64_t nnz, int64_t nstored, const uint32_t *part, int32_t *rowptr,
+                  int32_t *colind, int32_t *seg);
+// out[e] = vals[src[seg[e]]] + ... + vals[src[seg[e + 1] - 1]], left to right in T (src == nullptr: the identity)
+template <class T> void coo_segment_sums(hipStream_t s, const T *vals, const int32_t *src, const int32_t *seg, int64_t nstored, T *out);
 // dst[i + c ld_dst] = src[idx[i] + c ld_src], i < n, c < ncols: rows of `esz`-byte elements (4, 8 or 16) picked through an index
 // vector -- the permutation of a reordered operator applied to vectors on their way in (idx = perm) and out (idx = inverse)
 void gather_rows(hipStream_t s, size_t esz, void *dst, int64_t ld_dst, const void *src, int64_t ld_src, const int32_t *idx, int64_t n,

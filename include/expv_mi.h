@@ -207,10 +207,34 @@ int expv_mi_op_create_csr_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t n
                               const void *vals, int idx_bytes, int index_base, int loc, expv_mi_op_t *op);
 int expv_mi_op_create_csc_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnz, const void *colptr, const void *rowval,
                               const void *nzval, int idx_bytes, int index_base, int loc, expv_mi_op_t *op);
-/* How a sparse operator came to be: out[0] 1 = created from device arrays; out[1] bytes of pattern brought to the host; out[2]
- * bytes of VALUES brought to the host (0 when every row is sorted and free of duplicates); out[3] the whole creation and out[4] the
- * ingest kernels + status read-back, in microseconds; out[5] 1 = ordering plan taken from the plan cache; out[6..7] 0.  An operator
- * created from host arrays reports zeros. */
+/* A sparse operator from coordinate triplets (row[k], col[k], vals[k]), k < nnz -- torch.sparse_coo, sparse(I, J, V, n, n), a
+ * ROCSparseMatrixCOO, the output of a finite-element assembly: indices idx_bytes = 4 or 8 wide with index base 0 or 1, values of
+ * `dtype`, each array 8-byte aligned at least.  The entries may come in ANY ORDER and may REPEAT a coordinate.  The operator is
+ * that of the matrix with a_ij = the sum of the entries whose coordinates are (i, j); the sum is taken in the operator's element
+ * type IN ASCENDING ORDER OF THE ENTRY'S POSITION k in the caller's arrays (complex types: real and imaginary parts separately).
+ * That order is part of the contract: the same triplets give the same bits, whatever the device did in between.  A sum that comes
+ * out as zero stays a stored entry (as in sparse(I, J, V) and scipy); expv_mi_op_info reports the number of DISTINCT coordinates
+ * as nnz.  nnz = 0 with n > 0 is the zero operator.
+ *   - loc = EXPV_MI_DEVICE: device pointers on the context's device, read during the call only.  loc = EXPV_MI_HOST: the three
+ *     arrays are staged into device memory and take the same path -- one implementation, the same bits.
+ *   - Both index arrays are range-checked on the device before anything indexes by them; an index outside [0, n) (after the base is
+ *     taken off) returns EXPV_MI_ARGUMENT_ERROR, "row index out of range" / "column index out of range" + the smallest offending
+ *     position, and *op is untouched.
+ *   - Sorting (stable radix sort by (row, col)), coalescing and compression to CSR run on the device; from the checked CSR arrays
+ *     on the operator is the one expv_mi_op_create_csr_loc makes of them (the pattern visits the host once, the values never do).
+ *     Entries that arrive strictly ascending by (row, col) skip the sort and the summation; entries that arrive non-descending
+ *     (adjacent repeats only) skip the sort.
+ *   - expv_mi_op_update_values on such an operator takes the values of ALL the triplets handed over at creation (out[6] of
+ *     expv_mi_op_ingest_info), in the caller's triplet order; they are summed exactly as at creation: the result is bit-equal to
+ *     creating the operator anew.  For this the operator keeps 4 (triplets + distinct coordinates + 1) bytes of device memory
+ *     (nothing when the triplets arrived strictly ascending). */
+int expv_mi_op_create_coo_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnz, const void *row, const void *col, const void *vals,
+                              int idx_bytes, int index_base, int loc, expv_mi_op_t *op);
+/* How a sparse operator came to be: out[0] 1 = created from device arrays (or triplets); out[1] bytes of pattern brought to the
+ * host; out[2] bytes of VALUES brought to the host (0 when every row is sorted and free of duplicates); out[3] the whole creation
+ * and out[4] the ingest kernels + status read-back (triplets: check, sort, compress and sums, by device events), in microseconds;
+ * out[5] 1 = ordering plan taken from the plan cache; out[6] the triplets handed to expv_mi_op_create_coo_loc (0 for CSR / CSC
+ * born operators); out[7] the sort passes that ran for them.  An operator created from host CSR / CSC arrays reports zeros. */
 int expv_mi_op_ingest_info(expv_mi_op_t op, int64_t out[8]);
 /* Dense column-major n x n (Matrix{T}); `loc` = where A lives now. */
 int expv_mi_op_create_dense(expv_mi_ctx_t ctx, int dtype, int64_t n, const void *A, int64_t lda, int loc,
@@ -230,7 +254,8 @@ int expv_mi_op_create_callback(expv_mi_ctx_t ctx, int dtype, int64_t n, expv_mi_
  * dtype in the order of the arrays the operator was created from (nzval order for op_create_csc, vals order for
  * op_create_csr); loc = EXPV_MI_HOST or EXPV_MI_DEVICE.  The stored forms are refilled on the device and ishermitian /
  * opnorm(A, Inf) re-evaluated -- ~20x cheaper than destroy + create (n = 1e6, nnz = 5e6: 2.6 ms against 36-42 ms).  The reference
- * has no counterpart because it reads A at call time (mul!(y, A, x)); a caller that mutates A in place calls this instead. */
+ * has no counterpart because it reads A at call time (mul!(y, A, x)); a caller that mutates A in place calls this instead.
+ * An operator created from triplets takes one value per TRIPLET, in triplet order (see expv_mi_op_create_coo_loc). */
 int expv_mi_op_update_values(expv_mi_op_t op, const void *vals, int loc);
 int expv_mi_op_destroy(expv_mi_op_t op);
 /* size(A,1), nnz (NA of krylov_phiv_adaptive.jl:335-342), LinearAlgebra.ishermitian(A), opnorm(A,Inf) */

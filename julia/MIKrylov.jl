@@ -323,9 +323,18 @@ MIOperator(A::SparseMatrixCSC{T}) where {T <: MIScalar} = MIOperator(SparseMatri
 # without a copy as MIArray{Ti, 1}(pointer, (length,), false); 1-based like every Julia sparse type.  The index arrays are checked on
 # the device, only the pattern visits the host (the orderings and storage layouts are planned there), the values stay where they are.
 # The arrays are read during the call only.  update_values!(op, nzval::MIVector) refreshes the values in the same entry order.
+# format = :coo takes coordinate triplets instead: first vector = I, second = J, third = V (see the host method below).
 function MIOperator(rowptr::MIVector{Ti}, colval::MIVector{Ti}, nzval::MIVector{T}, n::Integer;
                     format::Symbol = :csr, index_base::Integer = 1) where {Ti <: Union{Int32, Int64}, T <: MIScalar}
-    format in (:csr, :csc) || throw(ArgumentError("MIOperator: format must be :csr or :csc"))
+    format in (:csr, :csc, :coo) || throw(ArgumentError("MIOperator: format must be :csr, :csc or :coo"))
+    if format == :coo      # rowptr = I, colval = J, nzval = V: the arrays of a ROCSparseMatrixCOO (rowInd, colInd, nzVal), or what an assembly left
+        length(rowptr) == length(colval) == length(nzval) || throw(DimensionMismatch("MIOperator: I, J and V must have the same length"))
+        r = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:expv_mi_op_create_coo_loc, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Ref{Ptr{Cvoid}}),
+                    ctx().h, dtype(T), n, length(nzval), rowptr.ptr, colval.ptr, nzval.ptr, sizeof(Ti), index_base, DEVICE, r), ctx().h)
+        return wrap_operator(T, r[])
+    end
     length(rowptr) == n + 1 || throw(DimensionMismatch("MIOperator: the pointer array must have n + 1 entries"))
     length(colval) == length(nzval) || throw(DimensionMismatch("MIOperator: index and value arrays must have the same length"))
     r = Ref{Ptr{Cvoid}}(C_NULL)
@@ -340,9 +349,33 @@ function MIOperator(rowptr::MIVector{Ti}, colval::MIVector{Ti}, nzval::MIVector{
     end
     wrap_operator(T, r[])
 end
+# values a triplet-born operator takes at a refresh: one per triplet of the creation (repeats included); otherwise one per stored entry
+nvalues(op::MIOperator) = (e = ingest_info(op).coo_entries; e > 0 ? e : op.nnz)
 function update_values!(op::MIOperator{T}, nzval::MIVector{T}) where {T <: MIScalar}      # new values on the device, the creation's entry order
-    length(nzval) == op.nnz || throw(DimensionMismatch("update_values!: nnz values expected"))
+    length(nzval) == nvalues(op) || throw(DimensionMismatch("update_values!: one value per entry of the creation expected"))
     check(ccall((:expv_mi_op_update_values, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), op.h, nzval.ptr, DEVICE), ctx().h)
+    n, nz, hm, on, dt = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Cdouble}(0), Ref{Cint}(0)
+    check(ccall((:expv_mi_op_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Cint}, Ref{Cdouble}, Ref{Cint}), op.h, n, nz, hm, on, dt), ctx().h)
+    op.herm = hm[] != 0
+    op.opnorm_inf = on[]
+    op
+end
+# sparse(I, J, V, n, n) without the detour: triplets in any order, entries of one coordinate ADDED -- in the element type, in
+# ascending order of their position (the order is part of the library's contract: the same triplets give the same bits) --, a sum
+# that comes out as zero stays stored.  The host arrays are staged into device memory and sorted / coalesced / compressed there,
+# the path the device arrays of the constructor above take with format = :coo.  update_values!(op, V) then takes one value per
+# triplet, in triplet order: a Jacobian re-assembled on a fixed mesh.
+function MIOperator(I::Vector{Ti}, J::Vector{Ti}, V::Vector{T}, n::Integer; index_base::Integer = 1) where {Ti <: Union{Int32, Int64}, T <: MIScalar}
+    length(I) == length(J) == length(V) || throw(DimensionMismatch("MIOperator: I, J and V must have the same length"))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:expv_mi_op_create_coo_loc, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Ti}, Ptr{Ti}, Ptr{T}, Cint, Cint, Cint, Ref{Ptr{Cvoid}}),
+                ctx().h, dtype(T), n, length(V), I, J, V, sizeof(Ti), index_base, HOST, r), ctx().h)
+    wrap_operator(T, r[])
+end
+function update_values!(op::MIOperator{T}, V::Vector{T}) where {T <: MIScalar}            # new values on the host, the creation's entry order
+    length(V) == nvalues(op) || throw(DimensionMismatch("update_values!: one value per entry of the creation expected"))
+    check(ccall((:expv_mi_op_update_values, lib), Cint, (Ptr{Cvoid}, Ptr{T}, Cint), op.h, V, HOST), ctx().h)
     n, nz, hm, on, dt = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Cdouble}(0), Ref{Cint}(0)
     check(ccall((:expv_mi_op_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Cint}, Ref{Cdouble}, Ref{Cint}), op.h, n, nz, hm, on, dt), ctx().h)
     op.herm = hm[] != 0
@@ -354,7 +387,7 @@ function ingest_info(op::MIOperator)
     out = zeros(Int64, 8)
     check(ccall((:expv_mi_op_ingest_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), op.h, out), ctx().h)
     (from_device = out[1] != 0, pattern_bytes_to_host = out[2], value_bytes_to_host = out[3], create_s = 1.0e-6 * out[4],
-     ingest_s = 1.0e-6 * out[5], plan_cached = out[6] != 0)
+     ingest_s = 1.0e-6 * out[5], plan_cached = out[6] != 0, coo_entries = out[7], sort_passes = out[8])
 end
 function MIOperator(A::Matrix{T}) where {T <: MIScalar}
     r = Ref{Ptr{Cvoid}}(C_NULL)
