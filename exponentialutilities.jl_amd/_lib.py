@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("EXPV_MI_LIB") or os.path.join(HERE, "libexpv_mi.so") 
 
 F64, C64, F32, C32 = 0, 1, 2, 3
 HOST, DEVICE = 0, 1
+BSR_BLOCK_ROW_MAJOR, BSR_BLOCK_COL_MAJOR, BSR_COMPRESSED_COLS = 0, 1, 2      # layout bits of expv_mi_op_create_bsr_loc
 ORTHO_AUTO, ORTHO_MGS, ORTHO_LOWSYNC, ORTHO_PIPELINED = 0, 1, 2, 3
 PATH_FLAGS = {"modular": 1, "two_kernel": 2, "pipeline": 4, "wave": 8, "overlapped": 16, "redo_serial": 32,
               "redo_wave_off": 64, "resident": 128, "patch": 256, "pipelined_lanczos": 512}
@@ -88,6 +89,7 @@ PROTOTYPES = {
     "expv_mi_op_create_csr_loc": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _pvp]),
     "expv_mi_op_create_csc_loc": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _pvp]),
     "expv_mi_op_create_coo_loc": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _pvp]),
+    "expv_mi_op_create_bsr_loc": (_i, [_vp, _i, _i64, _i64, _i, _vp, _vp, _vp, _i, _i, _i, _i, _pvp]),
     "expv_mi_op_ingest_info": (_i, [_vp, _vp]),
     "expv_mi_op_create_dense": (_i, [_vp, _i, _i64, _vp, _i64, _i, _pvp]),
     "expv_mi_op_create_callback": (_i, [_vp, _i, _i64, MATVEC_FN, _vp, _i, _i64, _pvp]),

@@ -442,6 +442,76 @@ def _coo_index_arrays(row, col):
     return row, col
 
 
+def _is_torch_bsr(A):
+    if not _is_torch_sparse(A):
+        return False
+    import torch
+    return A.layout in (torch.sparse_bsr, torch.sparse_bsc)
+
+
+def _unpack_torch_bsr(A):
+    """The parts of a 2-D, square, non-batched ``torch.sparse_bsr`` / ``torch.sparse_bsc`` tensor with square blocks, on whatever
+    device it lives: ``(compressed, ptr, idx, vals, shape, bd)`` with compressed "rows" (ptr = crow_indices, idx = col_indices) or
+    "cols" (ptr = ccol_indices, idx = row_indices), the index tensors int32 or int64 and contiguous, the values ``(nnzb, bd, bd)``
+    contiguous -- torch stores row-major blocks in both layouts.  No copy of anything that is contiguous already; nothing moves
+    between devices."""
+    import torch
+    if A.layout == torch.sparse_bsr:
+        compressed, ptr, idx = "rows", A.crow_indices(), A.col_indices()
+    elif A.layout == torch.sparse_bsc:
+        compressed, ptr, idx = "cols", A.ccol_indices(), A.row_indices()
+    else:
+        raise TypeError(f"block-sparse torch tensors must have layout torch.sparse_bsr or torch.sparse_bsc, not {A.layout}")
+    if A.dim() != 2 or ptr.dim() != 1:
+        raise DimensionMismatch("a sparse operator is one 2-D matrix (no batch dimensions)")
+    if A.shape[0] != A.shape[1]:
+        raise DimensionMismatch("operator must be square")
+    vals = A.values()
+    if vals.dim() != 3:
+        raise DimensionMismatch("a sparse operator has scalar entries (no dense dimensions)")
+    if vals.shape[1] != vals.shape[2]:
+        raise DimensionMismatch(f"a block-sparse operator has square blocks, not {int(vals.shape[1])} x {int(vals.shape[2])} "
+                                "(convert with .to_sparse_csr())")
+    if vals.dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
+        raise TypeError(f"sparse operator values must be float32 / float64 / complex64 / complex128, not {vals.dtype}")
+    if ptr.dtype != idx.dtype or ptr.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"sparse operator indices must be int32 or int64, not {ptr.dtype} / {idx.dtype}")
+    return compressed, ptr.contiguous(), idx.contiguous(), vals.contiguous(), (int(A.shape[0]), int(A.shape[1])), int(vals.shape[1])
+
+
+def _bsr_index_arrays(ptr, idx):
+    """the two index arrays of a block-compressed matrix as the library takes them: both int32 or both int64, contiguous, 1-D,
+    where they lie (tensors on the GPU stay tensors, anything else becomes a numpy array)"""
+    if _is_torch(ptr) != _is_torch(idx):
+        raise TypeError("from_bsr: ptr and idx must both be torch tensors or both be arrays")
+    if _is_torch(ptr):
+        import torch
+        if ptr.device != idx.device:
+            raise ValueError("from_bsr: ptr and idx live on different devices")
+        if ptr.dtype != idx.dtype or ptr.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"sparse operator indices must be int32 or int64, not {ptr.dtype} / {idx.dtype}")
+        ptr, idx = ptr.contiguous(), idx.contiguous()
+        if not ptr.is_cuda:
+            ptr, idx = ptr.numpy(), idx.numpy()
+    else:
+        ptr, idx = np.asarray(ptr), np.asarray(idx)
+        if ptr.dtype != idx.dtype or ptr.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise TypeError(f"sparse operator indices must be int32 or int64, not {ptr.dtype} / {idx.dtype}")
+        ptr, idx = np.ascontiguousarray(ptr), np.ascontiguousarray(idx)
+    if ptr.ndim != 1 or idx.ndim != 1 or ptr.shape[0] < 1:
+        raise DimensionMismatch("from_bsr: ptr and idx must be vectors, ptr of one entry per block row (column) plus one")
+    return ptr, idx
+
+
+def _same_index_array(a, b):
+    """two index arrays, each a GPU tensor or a numpy array, hold the same integers"""
+    if _is_torch(a) and _is_torch(b) and a.device == b.device:
+        import torch
+        return a.shape == b.shape and bool(torch.equal(a.to(torch.int64), b.to(torch.int64)))
+    a, b = (x.cpu().numpy() if _is_torch(x) else np.asarray(x) for x in (a, b))
+    return np.array_equal(a, b)
+
+
 def _torch_sparse_to_scipy(A):
     """a CPU torch.sparse_csr / sparse_csc tensor as the scipy matrix of the same format (shares the arrays)"""
     import scipy.sparse as sp
@@ -468,16 +538,22 @@ class MIOperator:
     ``MIOperator.from_coo(A)`` for a ``torch.sparse_coo`` tensor (coalesced or not, on either side; ``expv(t, A, b)`` and the
     other front ends take such a tensor as ``A`` directly) and ``MIOperator.from_coo(row, col, vals, n)`` for arrays; repeated
     coordinates are added in entry order (expv_mi_op_create_coo_loc).  ``MIOperator(A)`` itself keeps refusing the layout.  A scipy ``coo_matrix`` keeps going through ``.tocsr()``, whose sum has scipy's order --
-    ``from_coo`` is the way to the entry-order sum.  Exposes ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian),
+    ``from_coo`` is the way to the entry-order sum.  Block-compressed matrices with square blocks (``torch.sparse_bsr`` /
+    ``sparse_bsc`` tensors, scipy's ``bsr_matrix``, or the three arrays) come in through ``MIOperator.from_bsr``
+    (expv_mi_op_create_bsr_loc) and the front ends take such a tensor as ``A`` too; a scipy ``bsr_matrix`` handed to the plain
+    constructor or front ends keeps going through ``.tocsc()``.  Exposes ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian),
     ``nnz`` and ``opnorm_inf``.
     """
 
-    def __init__(self, A, ctx=None, dtype=None, ishermitian=None, matvec=None, shape=None, matvec_c=None, _coo=None):
+    def __init__(self, A, ctx=None, dtype=None, ishermitian=None, matvec=None, shape=None, matvec_c=None, _coo=None, _bsr=None):
         lib = L.load()
         self.ctx = ctx or default_context()
         if _is_torch_coo(A):                           # triplets are handed over by name: the constructor stays with compressed layouts
             raise TypeError("MIOperator(A) takes sparse torch tensors of layout torch.sparse_csr or torch.sparse_csc; a "
                             f"{A.layout} tensor holds coordinate triplets: MIOperator.from_coo(A), or pass it to expv / phiv / ... as A")
+        if _is_torch_bsr(A):                           # ... and so are blocks
+            raise TypeError("MIOperator(A) takes sparse torch tensors of layout torch.sparse_csr or torch.sparse_csc; a "
+                            f"{A.layout} tensor holds blocks: MIOperator.from_bsr(A), or pass it to expv / phiv / ... as A")
         if _is_torch_sparse(A) and not A.is_cuda:      # a host matrix in torch's clothes: the scipy path
             A = _torch_sparse_to_scipy(A)
         self.src = A
@@ -485,7 +561,9 @@ class MIOperator:
         self._cb = None
         if _coo is not None:
             dt = self._create_coo(lib, h, *_coo, dtype=dtype)
-        elif matvec_c is not None:        # matrix-free, compiled: (function pointer of type expv_mi_matvec_fn, user pointer) -- what a Julia
+        elif _bsr is not None:
+            dt = self._create_bsr(lib, h, *_bsr, dtype=dtype)
+        elif matvec_c is not None:       # matrix-free, compiled: (function pointer of type expv_mi_matvec_fn, user pointer) -- what a Julia
             fn, user = matvec_c         # host passes as a @cfunction; nothing of Python runs inside the factorisation
             n = int(shape[0])
             dt = np.dtype(dtype or np.float64)
@@ -594,6 +672,8 @@ class MIOperator:
         try:            # element type the caller handed over (Float32 operands: see _ref_dtype)
             if _coo is not None:
                 self.src_dtype = _np_dtype_of(_coo[2]) if _is_torch(_coo[2]) else np.dtype(np.asarray(_coo[2]).dtype)
+            elif _bsr is not None:
+                self.src_dtype = _np_dtype_of(_bsr[2]) if _is_torch(_bsr[2]) else np.dtype(np.asarray(_bsr[2]).dtype)
             elif A is None:
                 self.src_dtype = np.dtype(dtype or np.float64)
             elif hasattr(A, "indptr") or isinstance(A, np.ndarray):
@@ -662,6 +742,72 @@ class MIOperator:
                                              ptrs[2] if nent else None, isz, int(index_base), loc, C.byref(h)), self.ctx._h)
         return dt
 
+    @classmethod
+    def from_bsr(cls, ptr, idx=None, vals=None, n=None, index_base=0, compressed="rows", block_order="row", ctx=None, dtype=None):
+        """``from_bsr(A)``: the operator of a 2-D, square ``torch.sparse_bsr`` / ``torch.sparse_bsc`` tensor with square blocks, on
+        the GPU or the CPU, or of a scipy ``bsr_matrix`` with square blocks.  ``from_bsr(ptr, idx, vals)``: the operator of the
+        block-compressed arrays (expv_mi_op_create_bsr_loc), numpy arrays or torch tensors: ``ptr`` over the block rows
+        (``compressed="rows"``, BSR) or block columns (``"cols"``, BSC), ``idx`` the block columns (rows), int32 or int64 with the
+        given base, ``vals`` of shape ``(nnzb, bd, bd)`` holding each block row-major (``block_order="row"``: torch, scipy) or
+        column-major (``"col"``); ``n`` defaults to ``(len(ptr) - 1) * bd``.  The operator is the scalar matrix of scipy's
+        ``bsr_matrix((vals, idx, ptr)).tocsr()``: every element of a stored block is a stored entry, zeros included.  Tensors on
+        the GPU are taken where they are (checked and expanded on the device; the values never visit the host unless a block row
+        is unsorted); host data is staged and takes the same path, so both give the same bits.  ``update_values`` then takes the
+        values in the same block order."""
+        if _is_torch_bsr(ptr) or (hasattr(ptr, "indptr") and getattr(ptr, "format", None) == "bsr"):
+            if idx is not None or vals is not None:
+                raise TypeError("from_bsr: either one block-sparse matrix or ptr, idx, vals")
+            if _is_torch_bsr(ptr):
+                compressed, ptr, idx, vals, shp, _ = _unpack_torch_bsr(ptr)
+            else:
+                A = ptr
+                if A.shape[0] != A.shape[1]:
+                    raise DimensionMismatch("operator must be square")
+                if A.blocksize[0] != A.blocksize[1]:
+                    raise DimensionMismatch(f"a block-sparse operator has square blocks, not {A.blocksize[0]} x {A.blocksize[1]} "
+                                            "(convert with .tocsr())")
+                compressed, ptr, idx, vals, shp = "rows", A.indptr, A.indices, A.data, tuple(int(x) for x in A.shape)
+            if n is not None and int(n) != shp[0]:
+                raise DimensionMismatch("from_bsr: n differs from the matrix's shape")
+            n, index_base, block_order = shp[0], 0, "row"
+        elif idx is None or vals is None:
+            raise TypeError("from_bsr: ptr, idx and vals are required")
+        if compressed not in ("rows", "cols") or block_order not in ("row", "col"):
+            raise ValueError('from_bsr: compressed is "rows" or "cols", block_order "row" or "col"')
+        return cls(None, ctx, dtype=dtype, _bsr=(ptr, idx, vals, n, int(index_base), compressed, block_order))
+
+    def _create_bsr(self, lib, h, ptr, idx, vals, n, index_base, compressed, block_order, dtype=None):
+        ptr, idx = _bsr_index_arrays(ptr, idx)
+        on_dev = _is_torch(ptr)
+        dt = _work_dtype((_np_dtype_of(vals) if _is_torch(vals) else np.asarray(vals).dtype) if dtype is None else dtype)
+        if on_dev:
+            import torch
+            if ptr.device.index not in (None, self.ctx.device):
+                raise ValueError(f"block arrays live on {ptr.device}, the context on device {self.ctx.device}")
+            vals = torch.as_tensor(vals, device=ptr.device)
+            if vals.dtype != _torch_dtype(dt):
+                vals = vals.to(_torch_dtype(dt))      # (on the device)
+            vals = vals.contiguous()
+            _torch_ready(ptr, idx, vals)
+            ptrs, nnzb, isz, loc = (ptr.data_ptr(), idx.data_ptr(), vals.data_ptr()), int(idx.numel()), ptr.element_size(), L.DEVICE
+        else:
+            if _is_torch(vals):
+                vals = vals.cpu().numpy()
+            vals = np.ascontiguousarray(vals, dtype=dt)
+            ptrs, nnzb, isz, loc = (ptr.ctypes.data, idx.ctypes.data, vals.ctypes.data), int(idx.shape[0]), ptr.dtype.itemsize, L.HOST
+        if vals.ndim != 3 or int(vals.shape[0]) != nnzb or vals.shape[1] != vals.shape[2] or int(vals.shape[1]) < 1:
+            raise DimensionMismatch("from_bsr: vals of shape (nnzb, bd, bd) expected, one square block per block index")
+        bd = int(vals.shape[1])
+        n = (int(ptr.shape[0]) - 1) * bd if n is None else int(n)
+        if n != (int(ptr.shape[0]) - 1) * bd:
+            raise DimensionMismatch("from_bsr: ptr must have n / bd + 1 entries")
+        layout = (L.BSR_BLOCK_COL_MAJOR if block_order == "col" else L.BSR_BLOCK_ROW_MAJOR) | (L.BSR_COMPRESSED_COLS if compressed == "cols" else 0)
+        self._sp_format, self._sp_sorted = "bsr", True
+        self._bsr_parts = (ptr, idx, vals, n, int(index_base), compressed, block_order)      # update_values compares, astype rebuilds
+        _check(lib.expv_mi_op_create_bsr_loc(self.ctx._h, _code(dt), n, nnzb, bd, ptrs[0], ptrs[1] if nnzb else None,
+                                             ptrs[2] if nnzb else None, isz, int(index_base), layout, loc, C.byref(h)), self.ctx._h)
+        return dt
+
     @property
     def reorder_info(self):
         """How the operator is stored (expv_mi_op_reorder_info): ``reordered`` -- as P A P' with P a bandwidth-reducing ordering
@@ -702,6 +848,8 @@ class MIOperator:
             raise ValueError("update_values: sparse operators only")
         if fmt == "coo":
             return self._update_coo(A)
+        if fmt == "bsr":
+            return self._update_bsr(A)
         if _is_torch_sparse(A):
             if not hasattr(self, "_dev_parts"):
                 raise ValueError("update_values: a sparse tensor refreshes an operator that was created from one")
@@ -768,10 +916,48 @@ class MIOperator:
             delattr(self, key)
         return self
 
+    def _update_bsr(self, A):
+        """update_values of an operator made from block arrays: the values in the block order of the creation -- a
+        ``(nnzb, bd, bd)`` or flat array or tensor, or a block-sparse matrix of the layout, shape, block size and indices of the
+        creation; permuted as at creation, bit-equal to creating anew"""
+        ptr, idx, old, n, base, compressed, order = self._bsr_parts
+        nnzb, bd = int(old.shape[0]), int(old.shape[1])
+        if _is_torch_bsr(A) or (hasattr(A, "indptr") and getattr(A, "format", None) == "bsr"):
+            if _is_torch_bsr(A):
+                c2, p2, i2, vals, shp, bd2 = _unpack_torch_bsr(A)
+            else:
+                c2, p2, i2, vals, shp, bd2 = "rows", A.indptr, A.indices, A.data, tuple(A.shape), (A.blocksize[0] if A.blocksize[0] == A.blocksize[1] else -1)
+            same = (c2, tuple(shp), bd2, "row") == (compressed, self.shape, bd, order) and int(i2.shape[0]) == nnzb
+            if not (same and _same_index_array(p2 + base, ptr) and _same_index_array(i2 + base, idx)):
+                raise ValueError("update_values: a block-sparse matrix with the layout, shape, block size and indices of the creation required")
+        else:
+            vals = A
+        if _is_torch(vals) and not vals.is_cuda:
+            vals = vals.numpy()
+        vals = vals.contiguous() if _is_torch(vals) else np.ascontiguousarray(vals, dtype=self.dtype)
+        if tuple(vals.shape) not in ((nnzb, bd, bd), (nnzb * bd * bd,)):
+            raise DimensionMismatch("update_values: the values of the creation's blocks expected, (%d, %d, %d) or flat" % (nnzb, bd, bd))
+        arg = _Arg(vals.reshape(-1), self.dtype)
+        _check(L.load().expv_mi_op_update_values(self._h, arg.ptr, arg.loc), self.ctx._h)
+        self._bsr_parts = (ptr, idx, arg.keep.reshape(nnzb, bd, bd), n, base, compressed, order)
+        n_, nnz, herm, opn, dtc = C.c_int64(), C.c_int64(), C.c_int(), C.c_double(), C.c_int()
+        _check(L.load().expv_mi_op_info(self._h, C.byref(n_), C.byref(nnz), C.byref(herm), C.byref(opn), C.byref(dtc)))
+        self.ishermitian = bool(herm.value)
+        self.opnorm_inf = float(opn.value)
+        for key in [k for k in vars(self) if k.startswith("_as_")]:      # converted copies hold the old values
+            delattr(self, key)
+        return self
+
     def astype(self, dtype):
         dtype = _work_dtype(dtype)
         if dtype == self.dtype:
             return self
+        if getattr(self, "_sp_format", None) == "bsr":      # rebuilt from the kept block arrays (on the device when they are there)
+            key = "_as_" + dtype.name
+            if not hasattr(self, key):
+                ptr, idx, vals, n, base, compressed, order = self._bsr_parts
+                setattr(self, key, MIOperator.from_bsr(ptr, idx, vals, n, base, compressed, order, self.ctx, dtype=dtype))
+            return getattr(self, key)
         if getattr(self, "_sp_format", None) == "coo":      # rebuilt from the kept triplets (on the device when they are there)
             key = "_as_" + dtype.name
             if not hasattr(self, key):
@@ -848,6 +1034,8 @@ def _as_operator(A, want_dtype=None, ctx=None):
         op = A
     elif _is_torch_coo(A):          # coordinate triplets, coalesced or not, on either side (MIOperator.from_coo)
         op = MIOperator.from_coo(A, ctx=ctx)
+    elif _is_torch_bsr(A):          # block-compressed, on either side (MIOperator.from_bsr)
+        op = MIOperator.from_bsr(A, ctx=ctx)
     elif _is_torch(A):
         op = MIOperator(A, ctx)
     else:

@@ -1839,7 +1839,87 @@ void create_coo_device(Ctx *ctx, int dtype, int64_t n, int64_t nnz, const void *
                        },
                        out);
 }
+
+// Block-compressed arrays (BSR, or BSC with EXPV_MI_BSR_COMPRESSED_COLS) -> the checked block pattern (op_ingest.hip on the block
+// arrays: nb rows, indices in [0, nb)) -> the scalar CSR32 / CSC32 pattern and value order (op_bsr.hip), then the same tail.
+// loc = HOST stages the three arrays into HBM and takes the same path: one implementation, the same bits.
+void create_bsr_device(Ctx *ctx, int dtype, int64_t n, int64_t nnzb, int block_dim, const void *ptr, const void *idx, const void *vals,
+                       int idx_bytes, int index_base, int layout, int loc, expv_mi_op_t *out) {
+  const std::string who = "op_create_bsr";
+  const auto t_begin = std::chrono::steady_clock::now();
+  if (!out) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null output");
+  if (idx_bytes != 4 && idx_bytes != 8) fail(EXPV_MI_ARGUMENT_ERROR, who + ": idx_bytes must be 4 or 8");
+  if (layout & ~(EXPV_MI_BSR_BLOCK_COL_MAJOR | EXPV_MI_BSR_COMPRESSED_COLS)) fail(EXPV_MI_ARGUMENT_ERROR, who + ": unknown layout bits");
+  if (block_dim < 1) fail(EXPV_MI_ARGUMENT_ERROR, who + ": block_dim must be at least 1");
+  if (n < 0 || n > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, who + ": n out of range for CSR32");
+  if (n % block_dim != 0) fail(EXPV_MI_ARGUMENT_ERROR, who + ": n must be a multiple of block_dim");
+  if (nnzb < 0) fail(EXPV_MI_ARGUMENT_ERROR, who + ": negative nnzb");
+  const int64_t bd2 = (int64_t)block_dim * block_dim;      // (block_dim < 2^31: no overflow)
+  if (nnzb > 0x7fffffffLL / bd2) fail(EXPV_MI_ARGUMENT_ERROR, who + ": nnzb * block_dim^2 exceeds CSR32");
+  const bool csc = (layout & EXPV_MI_BSR_COMPRESSED_COLS) != 0;
+  const char *pname = csc ? "colptr" : "rowptr";
+  if (!ptr) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null " + pname);
+  if (nnzb > 0 && (!idx || !vals)) fail(EXPV_MI_ARGUMENT_ERROR, who + (csc ? ": null rowval / nzval" : ": null colind / vals"));
+  if (loc != EXPV_MI_DEVICE && loc != EXPV_MI_HOST) fail(EXPV_MI_ARGUMENT_ERROR, who + ": bad location");
+  check_device_dtype(dtype, who.c_str());
+  if (!ctx) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null context");
+  ctx->use();
+  const int64_t nb = n / block_dim, nnz = nnzb * bd2;
+  // inner-major blocks as the scalar order sees them: BSR wants the in-block row outermost, BSC the in-block column
+  const bool transposed = ((layout & EXPV_MI_BSR_BLOCK_COL_MAJOR) != 0) != csc;
+  hipStream_t s = ctx->stream;
+  const size_t vbytes = dtype == EXPV_MI_C64 ? 16 : dtype == EXPV_MI_F32 ? 4 : 8;
+  DevBuf sptr, sidx, sval;
+  if (loc == EXPV_MI_HOST) {
+    sptr.alloc((size_t)idx_bytes * (size_t)(nb + 1));
+    HIPCHECK(hipMemcpyAsync(sptr.p, ptr, sptr.bytes, hipMemcpyHostToDevice, s));
+    ptr = sptr.p;
+    if (nnzb > 0) {
+      sidx.alloc((size_t)idx_bytes * (size_t)nnzb);
+      sval.alloc(vbytes * (size_t)nnz);
+      HIPCHECK(hipMemcpyAsync(sidx.p, idx, sidx.bytes, hipMemcpyHostToDevice, s));
+      HIPCHECK(hipMemcpyAsync(sval.p, vals, sval.bytes, hipMemcpyHostToDevice, s));
+      idx = sidx.p;
+      vals = sval.p;
+    }
+  }
+  // the block arrays are a CSR pattern of nb rows: the same checks, the same kernels, the same status record
+  DevBuf bptr(sizeof(int32_t) * (size_t)(nb + 1)), bidx(sizeof(int32_t) * (size_t)std::max<int64_t>(nnzb, 1) + 16), st_dev(sizeof(dev::IngestStatus));
+  dev::ingest_indices(s, idx_bytes, ptr, idx, nb, nnzb, index_base, bptr.as<int32_t>(), bidx.as<int32_t>(), st_dev.as<dev::IngestStatus>());
+  dev::IngestStatus st;
+  HIPCHECK(hipMemcpyAsync(&st, st_dev.p, sizeof(st), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  auto at = [](unsigned long long pos) { return " (first at position " + std::to_string(pos) + ")"; };
+  if (st.flags & dev::INGEST_BAD_FIRST) fail(EXPV_MI_ARGUMENT_ERROR, who + ": " + pname + "[0] must equal the index base");
+  if (st.flags & dev::INGEST_DECREASING) fail(EXPV_MI_ARGUMENT_ERROR, who + ": " + pname + " must be non-decreasing" + at(st.first_ptr));
+  if (st.flags & dev::INGEST_BAD_NNZ) fail(EXPV_MI_ARGUMENT_ERROR, who + ": nnzb must equal " + pname + "[n / block_dim] - index base");
+  if (st.flags & dev::INGEST_BAD_INDEX)
+    fail(EXPV_MI_ARGUMENT_ERROR, (csc ? std::string("sparse operator: row index out of range") : who + ": column index out of range") + at(st.first_idx));
+  // from here on 0 = bptr[0] <= ... <= bptr[nb] = nnzb and every block index is in [0, nb)
+  DevBuf ptr32(sizeof(int32_t) * (size_t)(n + 1)), idx32(sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1) + 16), pval(vbytes * (size_t)std::max<int64_t>(nnz, 1) + 16);
+  dev::bsr_expand_pattern(s, bptr.as<int32_t>(), bidx.as<int32_t>(), nb, nnzb, block_dim, ptr32.as<int32_t>(), idx32.as<int32_t>());
+  dev::bsr_permute_values(s, (int)vbytes, bptr.as<int32_t>(), vals, nb, nnzb, block_dim, transposed, pval.p);
+  HIPCHECK(hipStreamSynchronize(s));
+  const auto t_ingest = std::chrono::steady_clock::now();
+  bidx.release();
+  // block rows strictly ascending <=> scalar rows strictly ascending (scalar row r of a block row lists, block after block, the
+  // columns idx[k] block_dim + c, c ascending)
+  finish_sparse_device(ctx, who, csc, dtype, n, nnz, ptr32, idx32, pval.p, st.desc_all == st.desc_starts, t_begin,
+                       (int64_t)std::chrono::duration<double, std::micro>(t_ingest - t_begin).count(),
+                       [&](Op &op) {      // what a value refresh in block order needs
+                         op.bsr_dim = block_dim;
+                         op.bsr_nnzb = nnzb;
+                         op.bsr_transposed = transposed;
+                         op.bsr_ptr = std::move(bptr);
+                       },
+                       out);
+}
 }  // namespace
+
+int expv_mi_op_create_bsr_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnzb, int block_dim, const void *ptr, const void *idx,
+                              const void *vals, int idx_bytes, int index_base, int layout, int loc, expv_mi_op_t *out) {
+  return guarded(ctx, [&] { create_bsr_device(ctx, dtype, n, nnzb, block_dim, ptr, idx, vals, idx_bytes, index_base, layout, loc, out); });
+}
 
 int expv_mi_op_create_csr_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnz, const void *rowptr, const void *colind, const void *vals,
                               int idx_bytes, int index_base, int loc, expv_mi_op_t *out) {
@@ -2067,6 +2147,19 @@ int expv_mi_op_update_values(expv_mi_op_t op, const void *vals, int loc) {
         if (!op->coo_sum.p) op->coo_sum.alloc(sizeof(T) * (size_t)op->nnz);
         dev::coo_segment_sums<T>(s, reinterpret_cast<const T *>(v), op->coo_src.as<int32_t>(), op->coo_seg.as<int32_t>(), op->nnz, op->coo_sum.as<T>());
         op_update_values_T<T, V>(*op, op->coo_sum.p, EXPV_MI_DEVICE);
+      } else if (op->bsr_dim > 0) {      // block-born: the caller's values in block order, permuted exactly as at creation, then the common refill
+        hipStream_t s = op->ctx->stream;
+        const void *v = vals;
+        if (loc == EXPV_MI_HOST) {
+          const size_t need = sizeof(T) * (size_t)op->nnz;
+          if (op->upd_stage.bytes < need) op->upd_stage.alloc(need + 16);
+          HIPCHECK(hipMemcpyAsync(op->upd_stage.p, vals, need, hipMemcpyHostToDevice, s));
+          v = op->upd_stage.p;
+        }
+        if (!op->bsr_val.p) op->bsr_val.alloc(sizeof(T) * (size_t)op->nnz + 16);
+        dev::bsr_permute_values(s, (int)sizeof(T), op->bsr_ptr.as<int32_t>(), v, op->n / op->bsr_dim, op->bsr_nnzb, op->bsr_dim, op->bsr_transposed,
+                                op->bsr_val.p);
+        op_update_values_T<T, V>(*op, op->bsr_val.p, EXPV_MI_DEVICE);
       } else {
         op_update_values_T<T, V>(*op, vals, loc);
       }

@@ -322,6 +322,13 @@ struct Op {
   int64_t coo_entries = 0;
   bool coo_map = false;
   DevBuf coo_src, coo_seg, coo_sum;
+  // block-born (capi.hip: create_bsr_device): what a value refresh in the caller's block order permutes through -- the block
+  // dimension (0: not block-born), the blocks handed over, whether the blocks are stored inner-major (op_bsr.hip: "transposed"),
+  // the normalised block pointer array (4 (n / bsr_dim + 1) bytes) -- and the buffer the permuted values go to (first refresh on)
+  int bsr_dim = 0;
+  int64_t bsr_nnzb = 0;
+  bool bsr_transposed = false;
+  DevBuf bsr_ptr, bsr_val;
   bool plan_cached = false;      // the ordering / patch plan came from the process-wide plan cache (capi.hip: OrderPlanCache)
   int64_t ring_sum = 0, ring_over128 = 0, ring_tiles = 0;      // sum of the ring lengths, tiles with a ring of more than 128 rows, tiles
   int ring_pad = 0;          // 0: no patch form

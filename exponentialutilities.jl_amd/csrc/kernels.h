@@ -127,6 +127,16 @@ void coo_compress(hipStream_t s, const unsigned long long *key, int64_t n, int64
                   int32_t *colind, int32_t *seg);
 // out[e] = vals[src[seg[e]]] + ... + vals[src[seg[e + 1] - 1]], left to right in T (src == nullptr: the identity)
 template <class T> void coo_segment_sums(hipStream_t s, const T *vals, const int32_t *src, const int32_t *seg, int64_t nstored, T *out);
+// ---- a caller's block-compressed arrays (BSR / BSC), checked by ingest_indices, expanded to the scalar pattern and value order
+//      (op_bsr.hip; capi.hip: create_bsr_device, expv_mi_op_update_values) ----
+int bsr_tile();                                  // scalar positions a workgroup expands (BSR_TILE)
+// checked zero-based block arrays bptr[nb + 1], bidx[nnzb] -> ptr32[nb block_dim + 1], idx32[nnzb block_dim^2] (16-byte aligned)
+void bsr_expand_pattern(hipStream_t s, const int32_t *bptr, const int32_t *bidx, int64_t nb, int64_t nnzb, int block_dim, int32_t *ptr32,
+                        int32_t *idx32);
+// vals[nnzb block_dim^2] of value_bytes-wide elements (4, 8 or 16; aligned to min(value_bytes, 8)) in block order -> out (16-byte
+// aligned) in the order of idx32; transposed: the blocks are stored inner-major (BSR column-major, BSC row-major)
+void bsr_permute_values(hipStream_t s, int value_bytes, const int32_t *bptr, const void *vals, int64_t nb, int64_t nnzb, int block_dim,
+                        bool transposed, void *out);
 // dst[i + c ld_dst] = src[idx[i] + c ld_src], i < n, c < ncols: rows of `esz`-byte elements (4, 8 or 16) picked through an index
 // vector -- the permutation of a reordered operator applied to vectors on their way in (idx = perm) and out (idx = inverse)
 void gather_rows(hipStream_t s, size_t esz, void *dst, int64_t ld_dst, const void *src, int64_t ld_src, const int32_t *idx, int64_t n,

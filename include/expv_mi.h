@@ -230,6 +230,41 @@ int expv_mi_op_create_csc_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t n
  *     (nothing when the triplets arrived strictly ascending). */
 int expv_mi_op_create_coo_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnz, const void *row, const void *col, const void *vals,
                               int idx_bytes, int index_base, int loc, expv_mi_op_t *op);
+/* A sparse operator from block-compressed arrays with SQUARE blocks -- torch.sparse_bsr / sparse_bsc, scipy's bsr_matrix, a
+ * ROCSparseMatrixBSR (rowPtr, colVal, nzVal, blockDim, dir): the Jacobian of a multi-component problem.  n is the SCALAR size, a
+ * multiple of block_dim; nb = n / block_dim block rows (BSR) or block columns (BSC, layout bit EXPV_MI_BSR_COMPRESSED_COLS).
+ * ptr[nb + 1] and idx[nnzb] are idx_bytes = 4 or 8 wide with index base 0 or 1, vals[nnzb * block_dim^2] of `dtype`, every array
+ * aligned to its own element size at least (for 16-byte complex values 8 bytes suffice).  The block
+ * holding element (r, c) at vals[k][r][c] is ROW-MAJOR (torch, scipy, rocSPARSE dir = row), at vals[k][c][r] COLUMN-MAJOR.
+ *   - The operator is the scalar matrix scipy's bsr_matrix((vals, idx, ptr)).tocsr() gives: EVERY element of every stored block is
+ *     a stored entry, zeros included, and expv_mi_op_info reports nnz = nnzb * block_dim^2.  A value-dependent pattern would break
+ *     the fixed map expv_mi_op_update_values relies on; a caller who wants stored zeros gone hands over CSR.  Block `k = ptr[bi] + kk`
+ *     of block row bi, cnt = ptr[bi + 1] - ptr[bi], puts its element (r, c) at scalar CSR position
+ *         block_dim^2 ptr[bi] + r block_dim cnt + kk block_dim + c,   column idx[k] block_dim + c,
+ *     rowptr[bi block_dim + r] = block_dim^2 ptr[bi] + r block_dim cnt (positions are formed in 64-bit arithmetic).  BSC is the same
+ *     with rows and columns exchanged and yields scalar CSC arrays.  Block indices inside a block row may be unsorted and may repeat:
+ *     the scalar rows are then unsorted / hold duplicates exactly as a CSR caller's would and take the same path (Hermitian test on
+ *     the host, expv_mi_op_ingest_info out[2]).  nnzb = 0 with n > 0 is the zero operator.
+ *   - Host-side checks, before any device work, EXPV_MI_ARGUMENT_ERROR "op_create_bsr: ...", in this order: null output; idx_bytes;
+ *     unknown layout bits; block_dim < 1; n out of range for CSR32; n not a multiple of block_dim; negative nnzb; nnzb * block_dim^2
+ *     exceeds CSR32; null ptr / idx / vals; bad loc.
+ *   - loc = EXPV_MI_DEVICE: device pointers on the context's device, read during the call only.  loc = EXPV_MI_HOST: the three
+ *     arrays are staged into device memory and take the same path -- one implementation, the same bits.
+ *   - The block arrays are checked on the device before anything indexes by them, as the pattern of an nb x nb CSR matrix:
+ *     ptr[0] == index_base, ptr non-decreasing, ptr[nb] - index_base == nnzb, every block index in [0, nb) -- nb, not n.  A
+ *     violation returns EXPV_MI_ARGUMENT_ERROR in the host creators' words (+ the first offending position), *op is untouched and
+ *     nothing else has run.  The expansion of the pattern and the permutation of the values into scalar order then run on the
+ *     device (op_bsr.hip); from the checked scalar arrays on the operator is the one expv_mi_op_create_csr_loc / _csc_loc makes of
+ *     them, and expv_mi_op_ingest_info reports like theirs (out[6] = out[7] = 0).
+ *   - expv_mi_op_update_values on such an operator takes nnzb * block_dim^2 values in the caller's block order and layout; the
+ *     result is bit-equal to creating the operator anew.  For this the operator keeps the normalised block pointer array,
+ *     4 (nb + 1) bytes of device memory, and from the first refresh on a buffer of nnz values that the permuted values go to. */
+enum { EXPV_MI_BSR_BLOCK_ROW_MAJOR = 0,   /* values inside a block: vals[k][r][c] (torch, scipy, rocSPARSE dir = row) */
+       EXPV_MI_BSR_BLOCK_COL_MAJOR = 1,   /* vals[k][c][r] (rocSPARSE / CUSPARSE dir = column) */
+       EXPV_MI_BSR_COMPRESSED_COLS = 2 }; /* BSC: ptr runs over block COLUMNS, idx holds block rows; OR-ed with the block order */
+int expv_mi_op_create_bsr_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnzb, int block_dim,
+                              const void *ptr, const void *idx, const void *vals,
+                              int idx_bytes, int index_base, int layout, int loc, expv_mi_op_t *op);
 /* How a sparse operator came to be: out[0] 1 = created from device arrays (or triplets); out[1] bytes of pattern brought to the
  * host; out[2] bytes of VALUES brought to the host (0 when every row is sorted and free of duplicates); out[3] the whole creation
  * and out[4] the ingest kernels + status read-back (triplets: check, sort, compress and sums, by device events), in microseconds;
@@ -255,7 +290,8 @@ int expv_mi_op_create_callback(expv_mi_ctx_t ctx, int dtype, int64_t n, expv_mi_
  * op_create_csr); loc = EXPV_MI_HOST or EXPV_MI_DEVICE.  The stored forms are refilled on the device and ishermitian /
  * opnorm(A, Inf) re-evaluated -- ~20x cheaper than destroy + create (n = 1e6, nnz = 5e6: 2.6 ms against 36-42 ms).  The reference
  * has no counterpart because it reads A at call time (mul!(y, A, x)); a caller that mutates A in place calls this instead.
- * An operator created from triplets takes one value per TRIPLET, in triplet order (see expv_mi_op_create_coo_loc). */
+ * An operator created from triplets takes one value per TRIPLET, in triplet order (see expv_mi_op_create_coo_loc); one created
+ * from block arrays takes nnzb * block_dim^2 values in block order and layout (see expv_mi_op_create_bsr_loc). */
 int expv_mi_op_update_values(expv_mi_op_t op, const void *vals, int loc);
 int expv_mi_op_destroy(expv_mi_op_t op);
 /* size(A,1), nnz (NA of krylov_phiv_adaptive.jl:335-342), LinearAlgebra.ishermitian(A), opnorm(A,Inf) */

@@ -349,6 +349,25 @@ function MIOperator(rowptr::MIVector{Ti}, colval::MIVector{Ti}, nzval::MIVector{
     end
     wrap_operator(T, r[])
 end
+# Block-compressed arrays with square blocks, already on the device: the fields of a ROCSparseMatrixBSR (rowPtr, colVal, nzVal,
+# blockDim, dir) -- block_dim is the fifth argument, format = :bsr (pointer array over block rows) or :bsc (over block columns),
+# block_order = :row (nzVal[r, c, k] row-major inside a block, dir = 'R') or :col (dir = 'C').  n is the scalar size.  The operator is
+# the scalar matrix with EVERY element of every stored block stored (op.nnz = length(nzval)); the block arrays are checked and
+# expanded on the device.  update_values!(op, nzval::MIVector) refreshes the values in the same block order and layout.
+function MIOperator(ptr::MIVector{Ti}, idx::MIVector{Ti}, nzval::MIVector{T}, n::Integer, block_dim::Integer;
+                    format::Symbol = :bsr, block_order::Symbol = :row, index_base::Integer = 1) where {Ti <: Union{Int32, Int64}, T <: MIScalar}
+    format in (:bsr, :bsc) || throw(ArgumentError("MIOperator: with a block dimension format must be :bsr or :bsc"))
+    block_order in (:row, :col) || throw(ArgumentError("MIOperator: block_order must be :row or :col"))
+    block_dim >= 1 && n % block_dim == 0 || throw(DimensionMismatch("MIOperator: n must be a multiple of block_dim"))
+    length(ptr) == div(n, block_dim) + 1 || throw(DimensionMismatch("MIOperator: the pointer array must have n / block_dim + 1 entries"))
+    length(nzval) == length(idx) * block_dim^2 || throw(DimensionMismatch("MIOperator: block_dim^2 values per block index expected"))
+    layout = (block_order == :col ? 1 : 0) | (format == :bsc ? 2 : 0)      # EXPV_MI_BSR_BLOCK_COL_MAJOR, EXPV_MI_BSR_COMPRESSED_COLS
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:expv_mi_op_create_bsr_loc, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ref{Ptr{Cvoid}}),
+                ctx().h, dtype(T), n, length(idx), block_dim, ptr.ptr, idx.ptr, nzval.ptr, sizeof(Ti), index_base, layout, DEVICE, r), ctx().h)
+    wrap_operator(T, r[])
+end
 # values a triplet-born operator takes at a refresh: one per triplet of the creation (repeats included); otherwise one per stored entry
 nvalues(op::MIOperator) = (e = ingest_info(op).coo_entries; e > 0 ? e : op.nnz)
 function update_values!(op::MIOperator{T}, nzval::MIVector{T}) where {T <: MIScalar}      # new values on the device, the creation's entry order
