@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("EXPV_MI_LIB") or os.path.join(HERE, "libexpv_mi.so") 
 F64, C64, F32, C32 = 0, 1, 2, 3
 HOST, DEVICE = 0, 1
 BSR_BLOCK_ROW_MAJOR, BSR_BLOCK_COL_MAJOR, BSR_COMPRESSED_COLS = 0, 1, 2      # layout bits of expv_mi_op_create_bsr_loc
+DIA_ALIGN_COL, DIA_ALIGN_ROW, DIA_ALIGN_START = 0, 1, 2                      # align of expv_mi_op_create_dia_loc
 ORTHO_AUTO, ORTHO_MGS, ORTHO_LOWSYNC, ORTHO_PIPELINED = 0, 1, 2, 3
 PATH_FLAGS = {"modular": 1, "two_kernel": 2, "pipeline": 4, "wave": 8, "overlapped": 16, "redo_serial": 32,
               "redo_wave_off": 64, "resident": 128, "patch": 256, "pipelined_lanczos": 512}
@@ -90,6 +91,7 @@ PROTOTYPES = {
     "expv_mi_op_create_csc_loc": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _pvp]),
     "expv_mi_op_create_coo_loc": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _pvp]),
     "expv_mi_op_create_bsr_loc": (_i, [_vp, _i, _i64, _i64, _i, _vp, _vp, _vp, _i, _i, _i, _i, _pvp]),
+    "expv_mi_op_create_dia_loc": (_i, [_vp, _i, _i64, _i, _vp, _vp, _i64, _i, _i, _pvp]),
     "expv_mi_op_ingest_info": (_i, [_vp, _vp]),
     "expv_mi_op_create_dense": (_i, [_vp, _i, _i64, _vp, _i64, _i, _pvp]),
     "expv_mi_op_create_callback": (_i, [_vp, _i, _i64, MATVEC_FN, _vp, _i, _i64, _pvp]),
@@ -145,6 +147,7 @@ PROTOTYPES = {
     "expv_mi_abi_sizeof": (C.c_size_t, [_i]),
     "expv_mi_abi_layout": (C.c_char_p, [_i]),
     "expv_mi_host_pattern_info": (_i, [C.c_int64, _vp, _vp, _i, _vp]),
+    "expv_mi_host_dia_pattern": (_i, [C.c_int64, _i, _vp, C.c_int64, _i, _vp, _vp, _vp, _vp]),
     "expv_mi_host_rcm": (_i, [C.c_int64, _vp, _vp, _i, _vp, _vp]),
     "expv_mi_host_wrapsum": (_i, [_vp, C.c_uint64, _vp]),
     "expv_mi_host_expm": (_i, [_i, _i, _vp, _i]),

@@ -31,7 +31,7 @@ __all__ = [
     "lanczos_", "expv", "expv_", "phiv", "phiv_", "expv_timestep", "expv_timestep_", "phiv_timestep",
     "phiv_timestep_", "kiops", "timestep_caches", "expv_batch", "expv_batch_multi", "RcclComm", "rccl_available", "rccl_unique_id", "ExpvMIError", "DimensionMismatch", "host_expm",
     "exponential", "exponential_", "mul_", "phi", "phi_", "balance_", "host_gebal",
-    "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
+    "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_dia_pattern", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
 ]
 
 ExpvMIError = L.ExpvMIError
@@ -512,6 +512,62 @@ def _same_index_array(a, b):
     return np.array_equal(a, b)
 
 
+_DIA_ALIGN = {"col": L.DIA_ALIGN_COL, "row": L.DIA_ALIGN_ROW, "start": L.DIA_ALIGN_START}
+
+
+def _is_scipy_dia(A):
+    return hasattr(A, "offsets") and hasattr(A, "data") and getattr(A, "format", None) == "dia"
+
+
+def _dia_from_scipy(A):
+    """``(data, offsets, n)`` of a square scipy ``dia_matrix`` / ``dia_array``, column-aligned as scipy stores it.  scipy allows
+    ``data.shape[1] < n``: the missing slots are absent entries, and the rows are padded with zeros here so that every in-matrix
+    position of a stored diagonal exists -- the same matrix."""
+    if A.shape[0] != A.shape[1]:
+        raise DimensionMismatch("operator must be square")
+    n = int(A.shape[0])
+    data, offsets = np.asarray(A.data), np.asarray(A.offsets, dtype=np.int64)
+    if data.shape[1] < n:
+        wide = np.zeros((data.shape[0], n), dtype=data.dtype)
+        wide[:, :data.shape[1]] = data
+        data = wide
+    return data, offsets, n
+
+
+def _dia_layout(data, dt):
+    """A 2-D ``data`` array of stored diagonals as the library takes it: ``(keep, ptr, ld, loc)``.  A torch tensor on the GPU stays
+    where it is, a CPU tensor or anything else is a numpy array on the host; the element type becomes ``dt``.  Rows must have unit
+    stride (``stride(1) == 1``); ``stride(0)`` is handed over as ld, so a view into a wider buffer is taken without a copy."""
+    if _is_torch(data) and not data.is_cuda:
+        data = data.detach().numpy()
+    if _is_torch(data):
+        if data.dim() != 2:
+            raise DimensionMismatch("from_dia: data must be 2-D, one row per stored diagonal")
+        if data.dtype != _torch_dtype(dt):
+            data = data.to(_torch_dtype(dt))      # (on the device)
+        rows, cols, s0, s1 = int(data.shape[0]), int(data.shape[1]), int(data.stride(0)), int(data.stride(1))
+        ptr, loc = data.data_ptr(), L.DEVICE
+    else:
+        data = np.asarray(data)
+        if data.ndim != 2:
+            raise DimensionMismatch("from_dia: data must be 2-D, one row per stored diagonal")
+        if data.dtype != dt:
+            data = data.astype(dt)
+        isz = data.dtype.itemsize
+        if data.strides[0] % isz or data.strides[1] % isz:
+            raise ValueError("from_dia: the strides of data must be whole elements")
+        rows, cols, s0, s1 = int(data.shape[0]), int(data.shape[1]), data.strides[0] // isz, data.strides[1] // isz
+        ptr, loc = data.ctypes.data, L.HOST
+    if rows == 0 or cols == 0:      # nothing stored: the strides of an empty array say nothing
+        return data, None, max(cols, 1), loc
+    if cols > 1 and s1 != 1:
+        raise ValueError(f"from_dia: the rows of data must have unit stride (stride(1) == 1), not {s1}: pass data.contiguous() "
+                         "or the transpose's copy")
+    if rows > 1 and s0 < cols:
+        raise ValueError(f"from_dia: stride(0) = {s0} of data is smaller than its row length {cols} (overlapping or reversed rows)")
+    return data, ptr, (s0 if rows > 1 else max(cols, 1)), loc
+
+
 def _torch_sparse_to_scipy(A):
     """a CPU torch.sparse_csr / sparse_csc tensor as the scipy matrix of the same format (shares the arrays)"""
     import scipy.sparse as sp
@@ -541,11 +597,13 @@ class MIOperator:
     ``from_coo`` is the way to the entry-order sum.  Block-compressed matrices with square blocks (``torch.sparse_bsr`` /
     ``sparse_bsc`` tensors, scipy's ``bsr_matrix``, or the three arrays) come in through ``MIOperator.from_bsr``
     (expv_mi_op_create_bsr_loc) and the front ends take such a tensor as ``A`` too; a scipy ``bsr_matrix`` handed to the plain
-    constructor or front ends keeps going through ``.tocsc()``.  Exposes ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian),
+    constructor or front ends keeps going through ``.tocsc()``.  Stored diagonals (a scipy ``dia_matrix``, or a 2-D tensor / array
+    with one row per diagonal and the offsets) come in through ``MIOperator.from_dia`` (expv_mi_op_create_dia_loc); the plain
+    constructor treats a scipy ``dia_matrix`` as before.  Exposes ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian),
     ``nnz`` and ``opnorm_inf``.
     """
 
-    def __init__(self, A, ctx=None, dtype=None, ishermitian=None, matvec=None, shape=None, matvec_c=None, _coo=None, _bsr=None):
+    def __init__(self, A, ctx=None, dtype=None, ishermitian=None, matvec=None, shape=None, matvec_c=None, _coo=None, _bsr=None, _dia=None):
         lib = L.load()
         self.ctx = ctx or default_context()
         if _is_torch_coo(A):                           # triplets are handed over by name: the constructor stays with compressed layouts
@@ -563,6 +621,8 @@ class MIOperator:
             dt = self._create_coo(lib, h, *_coo, dtype=dtype)
         elif _bsr is not None:
             dt = self._create_bsr(lib, h, *_bsr, dtype=dtype)
+        elif _dia is not None:
+            dt = self._create_dia(lib, h, *_dia, dtype=dtype)
         elif matvec_c is not None:       # matrix-free, compiled: (function pointer of type expv_mi_matvec_fn, user pointer) -- what a Julia
             fn, user = matvec_c         # host passes as a @cfunction; nothing of Python runs inside the factorisation
             n = int(shape[0])
@@ -674,6 +734,8 @@ class MIOperator:
                 self.src_dtype = _np_dtype_of(_coo[2]) if _is_torch(_coo[2]) else np.dtype(np.asarray(_coo[2]).dtype)
             elif _bsr is not None:
                 self.src_dtype = _np_dtype_of(_bsr[2]) if _is_torch(_bsr[2]) else np.dtype(np.asarray(_bsr[2]).dtype)
+            elif _dia is not None:
+                self.src_dtype = _np_dtype_of(_dia[0]) if _is_torch(_dia[0]) else np.dtype(np.asarray(_dia[0]).dtype)
             elif A is None:
                 self.src_dtype = np.dtype(dtype or np.float64)
             elif hasattr(A, "indptr") or isinstance(A, np.ndarray):
@@ -808,6 +870,51 @@ class MIOperator:
                                              ptrs[2] if nnzb else None, isz, int(index_base), layout, loc, C.byref(h)), self.ctx._h)
         return dt
 
+    @classmethod
+    def from_dia(cls, data, offsets=None, n=None, align="col", ctx=None, dtype=None):
+        """``from_dia(A)``: the operator of a square scipy ``dia_matrix`` / ``dia_array``.  ``from_dia(data, offsets, n)``: the
+        n x n operator of stored diagonals (expv_mi_op_create_dia_loc): ``offsets`` the diagonals' offsets k = column - row in any
+        order, ``data`` a 2-D torch tensor (GPU or CPU) or numpy array with one row per offset and unit stride along the rows
+        (``stride(0)`` may be larger than the row length: it is handed over as ld).  ``align`` says where element (i, i + k) lies
+        in its row: ``"col"`` at column i + k (scipy, LAPACK band rows), ``"row"`` at column i (the DIA of GPU sparse libraries),
+        ``"start"`` at column min(i, i + k) (compact vectors).  ``n`` defaults to the row length (``"start"``: plus the smallest
+        |k|).  The pattern is decided by the offsets alone: every in-matrix position of a stored diagonal is a stored entry,
+        zeros included -- scipy's ``.tocsr()`` without its dropping of zeros; slots that correspond to no matrix position are
+        never read.  A tensor on the GPU is expanded where it is; host data is staged and takes the same path.
+        ``update_values`` then takes a ``data`` array of the same shape, strides and alignment."""
+        if _is_scipy_dia(data):
+            if offsets is not None:
+                raise TypeError("from_dia: either one scipy dia matrix or data, offsets")
+            data, offsets, n2 = _dia_from_scipy(data)
+            if n is not None and int(n) != n2:
+                raise DimensionMismatch("from_dia: n differs from the matrix's shape")
+            n, align = n2, "col"
+        elif offsets is None:
+            raise TypeError("from_dia: data and offsets are required")
+        if align not in _DIA_ALIGN:
+            raise ValueError('from_dia: align is "col", "row" or "start"')
+        return cls(None, ctx, dtype=dtype, _dia=(data, offsets, n, align))
+
+    def _create_dia(self, lib, h, data, offsets, n, align, dtype=None):
+        offsets = np.ascontiguousarray(np.asarray(offsets.cpu() if _is_torch(offsets) else offsets), dtype=np.int64)
+        dt = _work_dtype((_np_dtype_of(data) if _is_torch(data) else np.asarray(data).dtype) if dtype is None else dtype)
+        data, ptr, ld, loc = _dia_layout(data, dt)
+        if offsets.ndim != 1 or int(data.shape[0]) != offsets.shape[0]:
+            raise DimensionMismatch("from_dia: one row of data per offset expected")
+        if loc == L.DEVICE:
+            if data.device.index not in (None, self.ctx.device):
+                raise ValueError(f"data lives on {data.device}, the context on device {self.ctx.device}")
+            _torch_ready(data)
+        if n is None:
+            n = int(data.shape[1]) + (int(np.abs(offsets).min()) if align == "start" and offsets.size else 0)
+        n = int(n)
+        self._sp_format, self._sp_sorted = "dia", True
+        self._dia_parts = (data, offsets, n, align, ld)      # update_values compares, astype rebuilds
+        _check(lib.expv_mi_op_create_dia_loc(self.ctx._h, _code(dt), n, int(offsets.shape[0]), offsets.ctypes.data,
+                                             ptr if data.shape[0] and data.shape[1] else None, ld, _DIA_ALIGN[align], loc, C.byref(h)),
+               self.ctx._h)
+        return dt
+
     @property
     def reorder_info(self):
         """How the operator is stored (expv_mi_op_reorder_info): ``reordered`` -- as P A P' with P a bandwidth-reducing ordering
@@ -850,6 +957,8 @@ class MIOperator:
             return self._update_coo(A)
         if fmt == "bsr":
             return self._update_bsr(A)
+        if fmt == "dia":
+            return self._update_dia(A)
         if _is_torch_sparse(A):
             if not hasattr(self, "_dev_parts"):
                 raise ValueError("update_values: a sparse tensor refreshes an operator that was created from one")
@@ -948,10 +1057,42 @@ class MIOperator:
             delattr(self, key)
         return self
 
+    def _update_dia(self, A):
+        """update_values of an operator made from stored diagonals: a ``data`` array or tensor of the creation's shape, strides
+        and alignment (padding is not read), or a scipy dia matrix of the creation's shape and offsets; transposed as at creation,
+        bit-equal to creating anew"""
+        old, offsets, n, align, ld = self._dia_parts
+        if _is_scipy_dia(A):
+            data, off2, n2 = _dia_from_scipy(A)
+            if n2 != n or align != "col" or not np.array_equal(off2, offsets):
+                raise ValueError("update_values: a dia matrix with the shape and offsets of the creation required")
+        else:
+            data = A
+        data, ptr, ld2, loc = _dia_layout(data, self.dtype)
+        if tuple(data.shape) != tuple(old.shape) or ld2 != ld:
+            raise DimensionMismatch("update_values: data of the creation's shape %s and row stride %d expected" % (tuple(old.shape), ld))
+        if loc == L.DEVICE:
+            _torch_ready(data)
+        _check(L.load().expv_mi_op_update_values(self._h, ptr if self.nnz else None, loc), self.ctx._h)
+        self._dia_parts = (data, offsets, n, align, ld)
+        n_, nnz, herm, opn, dtc = C.c_int64(), C.c_int64(), C.c_int(), C.c_double(), C.c_int()
+        _check(L.load().expv_mi_op_info(self._h, C.byref(n_), C.byref(nnz), C.byref(herm), C.byref(opn), C.byref(dtc)))
+        self.ishermitian = bool(herm.value)
+        self.opnorm_inf = float(opn.value)
+        for key in [k for k in vars(self) if k.startswith("_as_")]:      # converted copies hold the old values
+            delattr(self, key)
+        return self
+
     def astype(self, dtype):
         dtype = _work_dtype(dtype)
         if dtype == self.dtype:
             return self
+        if getattr(self, "_sp_format", None) == "dia":      # rebuilt from the kept diagonals (on the device when they are there)
+            key = "_as_" + dtype.name
+            if not hasattr(self, key):
+                data, offsets, n, align, _ = self._dia_parts
+                setattr(self, key, MIOperator.from_dia(data, offsets, n, align, self.ctx, dtype=dtype))
+            return getattr(self, key)
         if getattr(self, "_sp_format", None) == "bsr":      # rebuilt from the kept block arrays (on the device when they are there)
             key = "_as_" + dtype.name
             if not hasattr(self, key):
@@ -1996,6 +2137,26 @@ def host_pattern_info(A, dtype=np.float64):
                         "stencil: pipeline, patch form under context option patch (host_patch_order)")
     else:
         info["path"] = "two-kernel step"
+    return info
+
+
+def host_dia_pattern(offsets, n, ld=None, align="col", arrays=True):
+    """The scalar CSR pattern ``MIOperator.from_dia`` makes of stored diagonals and the creator's host-side checks (host only,
+    expv_mi_host_dia_pattern): ``nnz``, the ``diagonals`` with |k| < n and their smallest / largest offset, and with ``arrays``
+    ``rowptr``, ``colind`` and ``src`` -- the element index into ``data`` (rows of ``ld`` elements, default n) that each position
+    reads.  Raises what the creator would raise."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n, ld = int(n), int(n if ld is None else ld)
+    lib = L.load()
+    out = np.zeros(4, dtype=np.int64)
+    op = offsets.ctypes.data if offsets.size else None
+    _check(lib.expv_mi_host_dia_pattern(n, int(offsets.size), op, ld, _DIA_ALIGN[align], None, None, None, out.ctypes.data))
+    info = {"nnz": int(out[0]), "diagonals": int(out[1]), "min_offset": int(out[2]), "max_offset": int(out[3])}
+    if arrays:
+        rp, ci, src = np.zeros(n + 1, dtype=np.int32), np.zeros(info["nnz"], dtype=np.int32), np.zeros(info["nnz"], dtype=np.int64)
+        _check(lib.expv_mi_host_dia_pattern(n, int(offsets.size), op, ld, _DIA_ALIGN[align], rp.ctypes.data,
+                                            ci.ctypes.data if ci.size else None, src.ctypes.data if src.size else None, out.ctypes.data))
+        info.update(rowptr=rp, colind=ci, src=src)
     return info
 
 

@@ -1914,7 +1914,149 @@ void create_bsr_device(Ctx *ctx, int dtype, int64_t n, int64_t nnzb, int block_d
                        },
                        out);
 }
+
+// ---- stored diagonals (DIA / banded) ----------------------------------------------------------------------------------------
+// What the offsets decide, and every host-side check of expv_mi_op_create_dia_loc in the header's order: ONE function for the
+// creator and for expv_mi_host_dia_pattern, so the two cannot drift apart.  off: the offsets with |k| < n, ascending; base[r]: the
+// element index into `data` of row 0 of diagonal r (element (i, i + off[r]) at data[base[r] + i] under every alignment).
+struct DiaPlan {
+  int64_t nnz = 0;
+  std::vector<int32_t> off;
+  std::vector<int64_t> base;
+};
+void validate_dia(DiaPlan &P, const std::string &who, bool have_out, int64_t n, int ndiag, const int64_t *offsets, int64_t ld, int align, bool creator,
+                     const void *data, int loc) {
+  if (!have_out) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null output");
+  if (align != EXPV_MI_DIA_ALIGN_COL && align != EXPV_MI_DIA_ALIGN_ROW && align != EXPV_MI_DIA_ALIGN_START)
+    fail(EXPV_MI_ARGUMENT_ERROR, who + ": unknown align");
+  if (n < 0 || n > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, who + ": n out of range for CSR32");
+  if (ndiag < 0) fail(EXPV_MI_ARGUMENT_ERROR, who + ": negative ndiag");
+  if (ndiag > 0 && !offsets) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null offsets");
+  std::vector<std::pair<int64_t, int>> od((size_t)ndiag);      // (offset, the caller's row of data)
+  for (int d = 0; d < ndiag; ++d) od[(size_t)d] = {offsets[d], d};
+  std::sort(od.begin(), od.end());
+  for (int d = 1; d < ndiag; ++d)
+    if (od[(size_t)d].first == od[(size_t)d - 1].first) fail(EXPV_MI_ARGUMENT_ERROR, who + ": offset array contains duplicate values");
+  int64_t need = 0;      // the longest extent an in-range diagonal needs under `align`
+  for (const auto &e : od) {
+    const int64_t k = e.first;
+    if (k <= -n || k >= n) continue;      // contributes nothing, as in scipy
+    const int64_t len = n - (k < 0 ? -k : k);
+    P.nnz += len;                         // (< 2^31 diagonals of < 2^31 entries: no overflow)
+    need = std::max(need, align == EXPV_MI_DIA_ALIGN_COL ? (k > 0 ? n : n + k) : align == EXPV_MI_DIA_ALIGN_ROW ? (k >= 0 ? n - k : n) : len);
+    P.off.push_back((int32_t)k);
+  }
+  if (P.nnz > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, who + ": nnz exceeds CSR32");
+  if (ld < need) fail(EXPV_MI_ARGUMENT_ERROR, who + ": ld is smaller than a diagonal's extent");
+  if (ndiag > 0 && ld > (int64_t)(0x3fffffffffffffffLL / ndiag)) fail(EXPV_MI_ARGUMENT_ERROR, who + ": ld * ndiag out of range");
+  for (const auto &e : od) {
+    const int64_t k = e.first;
+    if (k <= -n || k >= n) continue;
+    P.base.push_back((int64_t)e.second * ld + (align == EXPV_MI_DIA_ALIGN_COL ? k : align == EXPV_MI_DIA_ALIGN_ROW ? 0 : std::min<int64_t>(k, 0)));
+  }
+  if (creator) {
+    if (P.nnz > 0 && !data) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null data");
+    if (loc != EXPV_MI_DEVICE && loc != EXPV_MI_HOST) fail(EXPV_MI_ARGUMENT_ERROR, who + ": bad location");
+  }
+}
+
+// A host `data` array staged for the value transposition: the same layout in device memory, but only the in-matrix segment of
+// every in-range diagonal is copied -- padding is not read here either.
+const void *stage_dia_host(hipStream_t s, size_t vbytes, int64_t n, const std::vector<int32_t> &off, const std::vector<int64_t> &base, const void *data,
+                           DevBuf &stage) {
+  int64_t extent = 0;
+  for (size_t r = 0; r < off.size(); ++r) extent = std::max(extent, base[r] + (off[r] < 0 ? n : n - off[r]));
+  const size_t want = vbytes * (size_t)extent + 16;
+  if (stage.bytes < want) stage.alloc(want);
+  for (size_t r = 0; r < off.size(); ++r) {
+    const int64_t ilo = off[r] < 0 ? -(int64_t)off[r] : 0, ihi = off[r] < 0 ? n : n - off[r];
+    const size_t at = vbytes * (size_t)(base[r] + ilo);
+    HIPCHECK(hipMemcpyAsync(static_cast<char *>(stage.p) + at, static_cast<const char *>(data) + at, vbytes * (size_t)(ihi - ilo), hipMemcpyHostToDevice, s));
+  }
+  return stage.p;
+}
+
+// Stored diagonals -> the scalar CSR32 pattern and value order (op_dia.hip), then the same tail.  Every check runs on the host, on
+// the offsets: nothing on the device is indexed by a value that was not checked.  loc = HOST stages `data` into HBM and takes the
+// same path: one implementation, the same bits.
+void create_dia_device(Ctx *ctx, int dtype, int64_t n, int ndiag, const int64_t *offsets, const void *data, int64_t ld, int align, int loc,
+                       expv_mi_op_t *out) {
+  const std::string who = "op_create_dia";
+  const auto t_begin = std::chrono::steady_clock::now();
+  DiaPlan P;
+  validate_dia(P, who, out != nullptr, n, ndiag, offsets, ld, align, true, data, loc);
+  check_device_dtype(dtype, who.c_str());
+  if (!ctx) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null context");
+  ctx->use();
+  hipStream_t s = ctx->stream;
+  const int q = (int)P.off.size();
+  const int64_t nnz = P.nnz;
+  const size_t vbytes = dtype == EXPV_MI_C64 ? 16 : dtype == EXPV_MI_F32 ? 4 : 8;
+  DevBuf sdata;
+  if (loc == EXPV_MI_HOST && nnz > 0) data = stage_dia_host(s, vbytes, n, P.off, P.base, data, sdata);
+  // the offsets table: q element indices of 8 bytes, then q offsets of 4
+  DevBuf table(12 * (size_t)std::max(q, 1) + 16);
+  std::vector<char> th(12 * (size_t)q);
+  if (q > 0) {
+    std::memcpy(th.data(), P.base.data(), 8 * (size_t)q);
+    std::memcpy(th.data() + 8 * (size_t)q, P.off.data(), 4 * (size_t)q);
+    HIPCHECK(hipMemcpyAsync(table.p, th.data(), th.size(), hipMemcpyHostToDevice, s));
+  }
+  const int64_t *base_d = table.as<int64_t>();
+  const int32_t *off_d = reinterpret_cast<const int32_t *>(static_cast<const char *>(table.p) + 8 * (size_t)q);
+  DevBuf ptr32(sizeof(int32_t) * (size_t)(n + 1)), idx32(sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1) + 16), pval(vbytes * (size_t)std::max<int64_t>(nnz, 1) + 16);
+  dev::dia_expand_pattern(s, off_d, q, n, nnz, ptr32.as<int32_t>(), idx32.as<int32_t>());
+  dev::dia_permute_values(s, (int)vbytes, data, base_d, off_d, q, n, nnz, pval.p);
+  HIPCHECK(hipStreamSynchronize(s));
+  const auto t_ingest = std::chrono::steady_clock::now();
+  sdata.release();
+  // rows sorted and free of duplicates by construction: distinct offsets in ascending order
+  finish_sparse_device(ctx, who, false, dtype, n, nnz, ptr32, idx32, pval.p, true, t_begin,
+                       (int64_t)std::chrono::duration<double, std::micro>(t_ingest - t_begin).count(),
+                       [&](Op &op) {      // what a value refresh in the caller's layout needs
+                         op.sdia_born = true;
+                         op.sdia_q = q;
+                         op.sdia_ndiag = ndiag;
+                         op.sdia_align = align;
+                         op.sdia_ld = ld;
+                         op.sdia_table = std::move(table);
+                         op.sdia_base = std::move(P.base);
+                         op.sdia_off = std::move(P.off);
+                       },
+                       out);
+}
 }  // namespace
+
+int expv_mi_op_create_dia_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int ndiag, const int64_t *offsets_host, const void *data, int64_t ld,
+                              int align, int loc, expv_mi_op_t *out) {
+  return guarded(ctx, [&] { create_dia_device(ctx, dtype, n, ndiag, offsets_host, data, ld, align, loc, out); });
+}
+
+int expv_mi_host_dia_pattern(int64_t n, int ndiag, const int64_t *offsets, int64_t ld, int align, int32_t *rowptr, int32_t *colind, int64_t *src,
+                             int64_t out[4]) {
+  return guarded(nullptr, [&] {
+    DiaPlan P;
+    validate_dia(P, "op_create_dia", out != nullptr, n, ndiag, offsets, ld, align, false, nullptr, 0);
+    const int q = (int)P.off.size();
+    out[0] = P.nnz;
+    out[1] = q;
+    out[2] = q ? P.off.front() : 0;
+    out[3] = q ? P.off.back() : 0;
+    if (!rowptr && !colind && !src) return;
+    int64_t p = 0;
+    for (int64_t i = 0; i < n; ++i) {      // the position contract, row by row: ascending in-range offsets with 0 <= i + k < n
+      if (rowptr) rowptr[i] = (int32_t)p;
+      for (int r = 0; r < q; ++r) {
+        const int64_t c = i + P.off[(size_t)r];
+        if (c < 0 || c >= n) continue;
+        if (colind) colind[p] = (int32_t)c;
+        if (src) src[p] = P.base[(size_t)r] + i;
+        ++p;
+      }
+    }
+    if (rowptr) rowptr[n] = (int32_t)p;
+  });
+}
 
 int expv_mi_op_create_bsr_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnzb, int block_dim, const void *ptr, const void *idx,
                               const void *vals, int idx_bytes, int index_base, int layout, int loc, expv_mi_op_t *out) {
@@ -2160,6 +2302,16 @@ int expv_mi_op_update_values(expv_mi_op_t op, const void *vals, int loc) {
         dev::bsr_permute_values(s, (int)sizeof(T), op->bsr_ptr.as<int32_t>(), v, op->n / op->bsr_dim, op->bsr_nnzb, op->bsr_dim, op->bsr_transposed,
                                 op->bsr_val.p);
         op_update_values_T<T, V>(*op, op->bsr_val.p, EXPV_MI_DEVICE);
+      } else if (op->sdia_born) {      // diagonal-born: the caller's ndiag x ld array, transposed exactly as at creation, then the common refill
+        hipStream_t s = op->ctx->stream;
+        const void *v = vals;
+        if (loc == EXPV_MI_HOST) v = stage_dia_host(s, sizeof(T), op->n, op->sdia_off, op->sdia_base, vals, op->upd_stage);
+        if (!op->sdia_val.p) op->sdia_val.alloc(sizeof(T) * (size_t)op->nnz + 16);
+        const int q = op->sdia_q;
+        dev::dia_permute_values(s, (int)sizeof(T), v, op->sdia_table.as<int64_t>(),
+                                reinterpret_cast<const int32_t *>(static_cast<const char *>(op->sdia_table.p) + 8 * (size_t)q), q, op->n, op->nnz,
+                                op->sdia_val.p);
+        op_update_values_T<T, V>(*op, op->sdia_val.p, EXPV_MI_DEVICE);
       } else {
         op_update_values_T<T, V>(*op, vals, loc);
       }

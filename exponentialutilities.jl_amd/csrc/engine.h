@@ -329,6 +329,15 @@ struct Op {
   int64_t bsr_nnzb = 0;
   bool bsr_transposed = false;
   DevBuf bsr_ptr, bsr_val;
+  // diagonal-born (capi.hip: create_dia_device): what a value refresh in the caller's ndiag x ld layout transposes through -- the
+  // in-range diagonals (0 with sdia_born: the zero operator), the caller's shape and alignment, the offsets table on the device
+  // (q element indices of 8 bytes, then q offsets of 4) -- and the buffer the transposed values go to (first refresh on)
+  bool sdia_born = false;
+  int sdia_q = 0, sdia_ndiag = 0, sdia_align = 0;
+  int64_t sdia_ld = 0;
+  DevBuf sdia_table, sdia_val;
+  std::vector<int64_t> sdia_base;      // the table once more on the host: a refresh from host data stages the in-matrix segments only
+  std::vector<int32_t> sdia_off;
   bool plan_cached = false;      // the ordering / patch plan came from the process-wide plan cache (capi.hip: OrderPlanCache)
   int64_t ring_sum = 0, ring_over128 = 0, ring_tiles = 0;      // sum of the ring lengths, tiles with a ring of more than 128 rows, tiles
   int ring_pad = 0;          // 0: no patch form

@@ -137,6 +137,18 @@ void bsr_expand_pattern(hipStream_t s, const int32_t *bptr, const int32_t *bidx,
 // aligned) in the order of idx32; transposed: the blocks are stored inner-major (BSR column-major, BSC row-major)
 void bsr_permute_values(hipStream_t s, int value_bytes, const int32_t *bptr, const void *vals, int64_t nb, int64_t nnzb, int block_dim,
                         bool transposed, void *out);
+// ---- a caller's stored diagonals (DIA / banded), checked on the host (capi.hip: validate_dia), expanded to the scalar pattern and
+//      value order (op_dia.hip; capi.hip: create_dia_device, expv_mi_op_update_values).  off[q]: the in-range offsets, strictly
+//      ascending; base[q]: the element index into `data` of row 0 of each of them ----
+int dia_tile();                                  // rows a workgroup of the value transposition owns (DIA_TILE)
+int dia_q_lds();                                 // in-range diagonals beyond which values are gathered, not staged in LDS (DIA_Q_LDS)
+int dia_rows(int q, int value_bytes);            // rows a workgroup owns for q in-range diagonals of value_bytes-wide elements
+// off[q] -> ptr32[n + 1], idx32[nnz] (16-byte aligned), nnz = sum over r of n - |off[r]|
+void dia_expand_pattern(hipStream_t s, const int32_t *off, int q, int64_t n, int64_t nnz, int32_t *ptr32, int32_t *idx32);
+// data of value_bytes-wide elements (4, 8 or 16; aligned to min(value_bytes, 8)) -> out (16-byte aligned) in the order of idx32;
+// only elements at base[r] + i with 0 <= i + off[r] < n are read
+void dia_permute_values(hipStream_t s, int value_bytes, const void *data, const int64_t *base, const int32_t *off, int q, int64_t n,
+                        int64_t nnz, void *out);
 // dst[i + c ld_dst] = src[idx[i] + c ld_src], i < n, c < ncols: rows of `esz`-byte elements (4, 8 or 16) picked through an index
 // vector -- the permutation of a reordered operator applied to vectors on their way in (idx = perm) and out (idx = inverse)
 void gather_rows(hipStream_t s, size_t esz, void *dst, int64_t ld_dst, const void *src, int64_t ld_src, const int32_t *idx, int64_t n,

@@ -265,11 +265,50 @@ enum { EXPV_MI_BSR_BLOCK_ROW_MAJOR = 0,   /* values inside a block: vals[k][r][c
 int expv_mi_op_create_bsr_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int64_t nnzb, int block_dim,
                               const void *ptr, const void *idx, const void *vals,
                               int idx_bytes, int index_base, int layout, int loc, expv_mi_op_t *op);
+/* A sparse operator from STORED DIAGONALS (DIA / banded storage) -- scipy's dia_matrix, LAPACK band rows, the DIA format of GPU
+ * sparse libraries, the vectors of a Tridiagonal: the operator of a method-of-lines discretisation.  offsets_host is ALWAYS a host
+ * array of ndiag offsets k = column - row, in any order.  data is ndiag rows of ld elements of `dtype`, lives where `loc` says, is
+ * aligned to its element size at least (8 bytes suffice for 16-byte complex) and is read during the call only; `align` says where
+ * in its row a diagonal's elements lie (the enum below).  All four element types.
+ *   - THE PATTERN IS DECIDED BY THE OFFSETS ALONE.  Every position of a stored diagonal that lies inside the matrix is a stored
+ *     entry, zeros included: a value-dependent pattern would break the fixed map expv_mi_op_update_values relies on (the same
+ *     decision as for block arrays).  As a matrix it equals scipy's dia_matrix((data, offsets)).tocsr(); scipy additionally drops
+ *     stored zeros, this library does not.  expv_mi_op_info reports nnz = sum over k of max(0, n - |k|).
+ *   - The position contract.  Offsets with |k| >= n contribute nothing, as in scipy.  Let s_0 < ... < s_{q-1} be the remaining
+ *     offsets in ascending order and d(r) the caller's row of `data` for s_r.  Scalar CSR row i lists, in ascending r, the entries
+ *     with 0 <= i + s_r < n, at column i + s_r, and
+ *         rowptr[i] = sum over r of clamp(min(i, n - s_r) - max(0, -s_r), 0, n - |s_r|)
+ *     (positions are formed in 64-bit arithmetic).  Rows are therefore always sorted and free of duplicates, whatever order the
+ *     caller's offsets come in.  expv_mi_op_ingest_info reports out[0] = 1, out[1] = 4 (n + 1 + nnz), out[2] = 0 (Hermitian test on
+ *     the device) and out[6] = out[7] = 0.
+ *   - PADDING IS NEVER READ.  The slots of `data` that correspond to no matrix position are not read and may hold anything, NaN
+ *     included: the first k (COL) or last k (ROW) slots of a diagonal, everything beyond a diagonal's extent up to ld, and the
+ *     whole row of an out-of-range offset.
+ *   - Host-side checks, before any device work, EXPV_MI_ARGUMENT_ERROR "op_create_dia: ...", *op untouched, in this order: null
+ *     output; unknown align; n out of range for CSR32; ndiag < 0; null offsets_host with ndiag > 0; duplicate offsets ("offset array
+ *     contains duplicate values", scipy's words); nnz exceeds CSR32; ld smaller than the longest extent an in-range diagonal needs
+ *     under `align` (COL: n for k > 0, n + k for k <= 0; ROW: n - k for k >= 0, n for k < 0; START: n - |k|); null data with
+ *     nnz > 0; bad loc.  Nothing else about the input can be wrong: no value is checked on the device.
+ *   - ndiag = 0, or every offset out of range, with n > 0 is the zero operator.
+ *   - loc = EXPV_MI_DEVICE: a device pointer on the context's device.  loc = EXPV_MI_HOST: the in-matrix segments of `data` are
+ *     staged into device memory and take the same path -- one implementation, the same bits.
+ *   - The pattern and the values are expanded on the device (op_dia.hip); from the scalar arrays on the operator is the one
+ *     expv_mi_op_create_csr_loc makes of them.
+ *   - expv_mi_op_update_values on such an operator takes a `data` array of the same ndiag x ld shape, alignment and offsets order,
+ *     never reads padding, and gives a result bit-equal to creating the operator anew.  For this the operator keeps the offsets
+ *     table (12 bytes per in-range diagonal, on the device and on the host) and from the first refresh on a buffer of nnz values. */
+enum { EXPV_MI_DIA_ALIGN_COL = 0,    /* element (i, i+k) of diagonal k at data[d*ld + (i+k)]: scipy dia_matrix, LAPACK band rows */
+       EXPV_MI_DIA_ALIGN_ROW = 1,    /* ... at data[d*ld + i]: the DIA of GPU sparse libraries */
+       EXPV_MI_DIA_ALIGN_START = 2 };/* ... at data[d*ld + min(i, i+k)]: compact vectors, Julia's Tridiagonal(dl, d, du) / k => v pairs */
+int expv_mi_op_create_dia_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int ndiag, const int64_t *offsets_host,
+                              const void *data, int64_t ld, int align, int loc, expv_mi_op_t *op);
 /* How a sparse operator came to be: out[0] 1 = created from device arrays (or triplets); out[1] bytes of pattern brought to the
  * host; out[2] bytes of VALUES brought to the host (0 when every row is sorted and free of duplicates); out[3] the whole creation
  * and out[4] the ingest kernels + status read-back (triplets: check, sort, compress and sums, by device events), in microseconds;
  * out[5] 1 = ordering plan taken from the plan cache; out[6] the triplets handed to expv_mi_op_create_coo_loc (0 for CSR / CSC
- * born operators); out[7] the sort passes that ran for them.  An operator created from host CSR / CSC arrays reports zeros. */
+ * born operators); out[7] the sort passes that ran for them.  An operator created from host CSR / CSC arrays reports zeros.  One
+ * created from stored diagonals (expv_mi_op_create_dia_loc) reports out[0] = 1, out[1] = 4 (n + 1 + nnz), out[2] = 0 always (its
+ * rows are sorted by construction), out[4] the table upload, the expansion kernels and the wait for them, out[6] = out[7] = 0. */
 int expv_mi_op_ingest_info(expv_mi_op_t op, int64_t out[8]);
 /* Dense column-major n x n (Matrix{T}); `loc` = where A lives now. */
 int expv_mi_op_create_dense(expv_mi_ctx_t ctx, int dtype, int64_t n, const void *A, int64_t lda, int loc,
@@ -291,7 +330,9 @@ int expv_mi_op_create_callback(expv_mi_ctx_t ctx, int dtype, int64_t n, expv_mi_
  * opnorm(A, Inf) re-evaluated -- ~20x cheaper than destroy + create (n = 1e6, nnz = 5e6: 2.6 ms against 36-42 ms).  The reference
  * has no counterpart because it reads A at call time (mul!(y, A, x)); a caller that mutates A in place calls this instead.
  * An operator created from triplets takes one value per TRIPLET, in triplet order (see expv_mi_op_create_coo_loc); one created
- * from block arrays takes nnzb * block_dim^2 values in block order and layout (see expv_mi_op_create_bsr_loc). */
+ * from block arrays takes nnzb * block_dim^2 values in block order and layout (see expv_mi_op_create_bsr_loc); one created from
+ * stored diagonals takes a `data` array of the creation's ndiag x ld shape, alignment and offsets order, whose padding is not read
+ * (see expv_mi_op_create_dia_loc). */
 int expv_mi_op_update_values(expv_mi_op_t op, const void *vals, int loc);
 int expv_mi_op_destroy(expv_mi_op_t op);
 /* size(A,1), nnz (NA of krylov_phiv_adaptive.jl:335-342), LinearAlgebra.ishermitian(A), opnorm(A,Inf) */
@@ -631,6 +672,13 @@ const char *expv_mi_abi_layout(int kind);
  * out[6] rows sorted and free of duplicates, out[7] slot cut-off of the SELL form (0: regular rows, every slice keeps its longest
  * row; > 0: irregular rows -- the entries of a row beyond the cut are applied from the CSR arrays by the overflow pass).  No reference counterpart (the reference stores CSC only). */
 int expv_mi_host_pattern_info(int64_t n, const int32_t *rowptr, const int32_t *colind, int dtype, int64_t out[8]);
+/* Host only: the scalar CSR pattern expv_mi_op_create_dia_loc makes of stored diagonals (its position contract), and its host-side
+ * checks -- the SAME validation function, with the same status and messages (read them with expv_mi_last_error(NULL)); the checks
+ * on `data` and `loc` have no counterpart here.  rowptr[n + 1], colind[nnz] and src[nnz] may each be NULL; src[p] is the element
+ * index into `data` that position p reads.  out = {nnz, in-range diagonals q, smallest in-range offset, largest in-range offset}
+ * (the offsets are 0 when q = 0); out is written before the arrays, so a first call with NULL arrays sizes them. */
+int expv_mi_host_dia_pattern(int64_t n, int ndiag, const int64_t *offsets, int64_t ld, int align,
+                             int32_t *rowptr, int32_t *colind, int64_t *src, int64_t out[4]);
 /* The ordering expv_mi_op_create_* would compute for this pattern (host only: reverse Cuthill-McKee on A + A'): perm[i] = the row
  * that becomes row i; out[0] / out[1] = max |col - row| before / after, out[2] / out[3] = step form before / after (3 single-pass
  * halo form, 2 wave form, 1 two-kernel step, 0 two-kernel step + overflow pass); out[2] has bit 8 (256) set when operator

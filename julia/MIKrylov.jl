@@ -368,6 +368,64 @@ function MIOperator(ptr::MIVector{Ti}, idx::MIVector{Ti}, nzval::MIVector{T}, n:
                 ctx().h, dtype(T), n, length(idx), block_dim, ptr.ptr, idx.ptr, nzval.ptr, sizeof(Ti), index_base, layout, DEVICE, r), ctx().h)
     wrap_operator(T, r[])
 end
+# Stored diagonals (DIA / banded storage, expv_mi_op_create_dia_loc): `data` holds one diagonal per COLUMN (Julia is column-major:
+# column d is row d of the C interface, size(data, 1) its ld), `offsets[d]` its offset k = column - row, in any order.  align says
+# where A[i, i + k] lies in its column: :col at (1-based) index i + k (the rows of a LAPACK band matrix, scipy's dia_matrix), :row
+# at index i (the DIA of GPU sparse libraries), :start at index min(i, i + k) (compact vectors, what Tridiagonal holds).  The
+# pattern is decided by the offsets alone -- every in-matrix position of a stored diagonal is a stored entry, zeros included, rows
+# sorted whatever the order of `offsets` -- and slots that correspond to no matrix position are never read.  The data of an MIMatrix
+# is expanded where it is; a host Matrix is staged and takes the same path.  update_values!(op, data) refreshes the values from an
+# array of the same size and alignment.
+const DIA_ALIGN = Dict(:col => 0, :row => 1, :start => 2)      # EXPV_MI_DIA_ALIGN_COL, _ROW, _START
+function dia_create(::Type{T}, n::Integer, offsets::Vector{Int64}, data, ldv::Integer, align::Symbol, loc::Integer) where {T <: MIScalar}
+    haskey(DIA_ALIGN, align) || throw(ArgumentError("MIOperator: align must be :col, :row or :start"))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve offsets data check(ccall((:expv_mi_op_create_dia_loc, lib), Cint,
+                                         (Ptr{Cvoid}, Cint, Int64, Cint, Ptr{Int64}, Ptr{Cvoid}, Int64, Cint, Cint, Ref{Ptr{Cvoid}}),
+                                         ctx().h, dtype(T), n, length(offsets), offsets, data, ldv, DIA_ALIGN[align], loc, r), ctx().h)
+    wrap_operator(T, r[])
+end
+function MIOperator(data::MIMatrix{T}, offsets::AbstractVector{<:Integer}, n::Integer; format::Symbol = :dia, align::Symbol = :col) where {T <: MIScalar}
+    format == :dia || throw(ArgumentError("MIOperator: a matrix of diagonals and their offsets take format = :dia"))
+    size(data, 2) == length(offsets) || throw(DimensionMismatch("MIOperator: one column of data per offset expected"))
+    dia_create(T, n, collect(Int64, offsets), data.ptr, ld(data), align, DEVICE)
+end
+function MIOperator(data::Matrix{T}, offsets::AbstractVector{<:Integer}, n::Integer; format::Symbol = :dia, align::Symbol = :col) where {T <: MIScalar}
+    format == :dia || throw(ArgumentError("MIOperator: a matrix of diagonals and their offsets take format = :dia"))
+    size(data, 2) == length(offsets) || throw(DimensionMismatch("MIOperator: one column of data per offset expected"))
+    dia_create(T, n, collect(Int64, offsets), pointer(data), max(size(data, 1), 1), align, HOST)
+end
+# LinearAlgebra's structured matrices: their vectors packed into :start alignment (column d = the diagonal from its first entry on)
+function dia_pack(::Type{T}, n::Integer, vecs) where {T}
+    data = zeros(T, max(n, 1), length(vecs))
+    for (d, v) in enumerate(vecs)
+        copyto!(view(data, 1:length(v), d), v)
+    end
+    data
+end
+dia_parts(A::Tridiagonal) = (Int64[-1, 0, 1], (A.dl, A.d, A.du))
+dia_parts(A::SymTridiagonal) = (m = size(A, 1) - 1; (Int64[-1, 0, 1], (view(A.ev, 1:m), A.dv, view(A.ev, 1:m))))      # (ev may have n entries)
+dia_parts(A::Bidiagonal) = (Int64[0, A.uplo == 'U' ? 1 : -1], (A.dv, A.ev))
+dia_parts(A::Diagonal) = (Int64[0], (A.diag,))
+const DiaStructured{T} = Union{Tridiagonal{T}, SymTridiagonal{T}, Bidiagonal{T}, Diagonal{T}}
+function MIOperator(A::DiaStructured{T}) where {T <: MIScalar}
+    n = size(A, 1)
+    offsets, vecs = dia_parts(A)
+    MIOperator(dia_pack(T, n, vecs), offsets, n; align = :start)
+end
+function update_values!(op::MIOperator{T}, data::Union{MIMatrix{T}, Matrix{T}}) where {T <: MIScalar}      # a diagonal-born operator: the creation's layout
+    loc = data isa MIMatrix ? DEVICE : HOST
+    GC.@preserve data check(ccall((:expv_mi_op_update_values, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), op.h, data isa MIMatrix ? data.ptr : pointer(data), loc), ctx().h)
+    n, nz, hm, on, dt = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Cdouble}(0), Ref{Cint}(0)
+    check(ccall((:expv_mi_op_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Cint}, Ref{Cdouble}, Ref{Cint}), op.h, n, nz, hm, on, dt), ctx().h)
+    op.herm = hm[] != 0
+    op.opnorm_inf = on[]
+    op
+end
+function update_values!(op::MIOperator{T}, A::DiaStructured{T}) where {T <: MIScalar}      # the same structured type as at creation
+    size(A, 1) == op.n || throw(DimensionMismatch("update_values!: same size as at creation required"))
+    update_values!(op, dia_pack(T, op.n, dia_parts(A)[2]))
+end
 # values a triplet-born operator takes at a refresh: one per triplet of the creation (repeats included); otherwise one per stored entry
 nvalues(op::MIOperator) = (e = ingest_info(op).coo_entries; e > 0 ? e : op.nnz)
 function update_values!(op::MIOperator{T}, nzval::MIVector{T}) where {T <: MIScalar}      # new values on the device, the creation's entry order
