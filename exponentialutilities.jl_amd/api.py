@@ -32,6 +32,7 @@ __all__ = [
     "phiv_timestep_", "kiops", "timestep_caches", "expv_batch", "expv_batch_multi", "RcclComm", "rccl_available", "rccl_unique_id", "ExpvMIError", "DimensionMismatch", "host_expm",
     "exponential", "exponential_", "mul_", "phi", "phi_", "balance_", "host_gebal",
     "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_dia_pattern", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
+    "expv_taylor", "expv_taylor_", "host_taylor_theta", "host_taylor_params",
 ]
 
 ExpvMIError = L.ExpvMIError
@@ -1432,6 +1433,72 @@ def expv(t, A, b=None, *, mode="happy_breakdown", **kw):
         expv.last_subspace = Ks
         return _round_to(w, _ref_dtype(_t_dtype(t), getattr(op, "src_dtype", op.dtype), bdt))     # same result type in every mode
     raise ValueError(f"Unknown Krylov iteration termination mode, {mode}")     # ArgumentError (:132)
+
+
+def _host_view(x):
+    """a torch tensor in host memory as the numpy array that shares its storage (anything else as it is)"""
+    return x.detach().numpy() if _is_torch(x) and not x.is_cuda else x
+
+
+_TAYLOR_INFO = ("m", "s", "applications", "early_stages", "launches", "host_reads", "path", "nonfinite_stage")
+
+
+def expv_taylor_(w, t, A, b, *, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """w <- exp(t A) b by the truncated Taylor series of Al-Mohy & Higham (expv_mi_expv_taylor; the reference's second expv
+    algorithm, ext/ExponentialUtilitiesStaticArraysExt.jl:124-163): no Krylov basis, no inner product, three work vectors, the
+    stopping rule decided on the device.  ``A``: anything an API call takes as an operator; ``b`` / ``w``: numpy, torch (either
+    side for ``b``), DeviceArray; they may be the same array.  ``precision``: None / 0 = the working precision of the operator's
+    real type, 1 = the 2^-24 table also for 64-bit operators.  ``max_matvecs`` > 0 refuses a call that would need more operator
+    applications (ArgumentError naming alpha, m*, s).  ``opnorm``: a bound on opnorm(A, Inf), needed by matrix-free operators
+    only.  A complex ``t`` needs a complex operator.  ``return_info``: also return the dictionary kept in
+    ``expv_taylor.last_info`` (m, s, applications, early_stages, launches, host_reads, path: 1 fused / 2 mul! + update,
+    nonfinite_stage, alpha, mu, normF)."""
+    tr, ti, _ = _t_parts(t)
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(b))
+    opT = _as_operator(op, T)
+    ba, wa = _Arg(_host_view(b), T), _Arg(_host_view(w), T, writable=True)
+    n = opT.shape[0]
+    if int(np.prod(ba.shape)) != n:
+        raise DimensionMismatch(f"length(b) [{int(np.prod(ba.shape))}] == size(A,1) [{n}] doesn't hold")
+    if int(np.prod(wa.shape)) != n:
+        raise DimensionMismatch(f"length(w) [{int(np.prod(wa.shape))}] == size(A,1) [{n}] doesn't hold")
+    info, dinfo = (C.c_int64 * 8)(), (C.c_double * 4)()
+    _check(L.load().expv_mi_expv_taylor(opT.ctx._h, opT._h, tr, ti, ba.ptr, ba.loc, wa.ptr, wa.loc, int(precision or 0),
+                                        int(max_matvecs), 0.0 if opnorm is None else float(opnorm), info, dinfo), opT.ctx._h)
+    wa.finish()
+    d = dict(zip(_TAYLOR_INFO, (int(v) for v in info)))
+    d.update(alpha=float(dinfo[0]), mu=complex(dinfo[1], dinfo[2]) if T.kind == "c" else float(dinfo[1]), normF=float(dinfo[3]))
+    expv_taylor.last_info = d
+    return (w, d) if return_info else w
+
+
+def expv_taylor(t, A, b, *, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """exp(t A) b by the truncated Taylor series (see expv_taylor_): the result lives where ``b`` does and has the element type
+    the device worked in (the operator's, complex when ``b`` is)."""
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(b))
+    if _is_torch(b) and not b.is_cuda:
+        import torch
+        w = torch.empty(b.shape[0], dtype=_torch_dtype(T))
+    else:
+        w = _empty_like(b, (b.shape[0],), T)
+    return expv_taylor_(w, t, op, b, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
+
+
+def host_taylor_theta(m, precision=0):
+    """theta_m (m = 1 .. 55) of the truncated-Taylor tables (expv_mi_host_taylor_theta; host only): precision 0 = tol 2^-53,
+    1 = tol 2^-24."""
+    th = C.c_double(0.0)
+    _check(L.load().expv_mi_host_taylor_theta(int(precision), int(m), C.byref(th)))
+    return float(th.value)
+
+
+def host_taylor_params(alpha, precision=0):
+    """(m*, s) of expv_taylor for alpha = |t| opnorm(A - mu I, Inf) (expv_mi_host_taylor_params; host only)."""
+    m, s = C.c_int(0), C.c_int64(0)
+    _check(L.load().expv_mi_host_taylor_params(int(precision), float(alpha), C.byref(m), C.byref(s)))
+    return int(m.value), int(s.value)
 
 
 def phiv_(w, t, Ks, k, *, correct=False, errest=False):

@@ -2760,6 +2760,55 @@ int expv_mi_expv_error_estimate(expv_mi_ks_t ks, expv_mi_op_t op, double t_re, d
   });
 }
 
+// ------------------------------------------------------------------ truncated Taylor series (expv_taylor.hip) ----
+int expv_mi_expv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc, void *w, int w_loc,
+                        int precision, int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4]) {
+  return guarded(ctx, [&] {
+    if (info) std::fill(info, info + 8, (int64_t)0);
+    if (dinfo) std::fill(dinfo, dinfo + 4, 0.0);
+    if (!ctx || !op) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: null context / operator");
+    if ((b_loc != EXPV_MI_HOST && b_loc != EXPV_MI_DEVICE) || (w_loc != EXPV_MI_HOST && w_loc != EXPV_MI_DEVICE))
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: unknown loc");
+    const int64_t n = op->n;
+    if (n == 0) return;
+    if (!b || !w) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: null pointer");
+    ctx->use();
+    const size_t esz = dtype_size(op->dtype), bytes = (size_t)n * esz;
+    DevBuf tmp, out;
+    const void *bd = vector_in(ctx, *op, b, b_loc, n, esz, tmp);
+    TaylorCall tc;
+    taylor_enqueue(ctx, *op, t_re, t_im, bd, precision, max_matvecs, opnorm, tc);
+    try {
+      // the result goes to the caller behind the last launch and shares the wait of the state read-back
+      hipStream_t s = ctx->stream;
+      const void *src = tc.F;
+      if (op->perm) {      // stored as P A P': rows back to their natural places
+        void *dst = w;
+        if (w_loc == EXPV_MI_HOST) { out.take_from(ctx, bytes + 16); dst = out.p; }
+        dev::gather_rows(s, esz, dst, n, tc.F, n, op->perm->pinv.as<int32_t>(), n, 1);
+        src = (w_loc == EXPV_MI_HOST) ? dst : nullptr;
+      }
+      if (src) HIPCHECK(hipMemcpyAsync(w, src, bytes, w_loc == EXPV_MI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+      taylor_collect(ctx, tc, info, dinfo);
+    } catch (...) {
+      (void)hipStreamSynchronize(ctx->stream);
+      throw;
+    }
+  });
+}
+int expv_mi_host_taylor_theta(int precision, int m, double *theta) {
+  return guarded(nullptr, [&] {
+    if (!theta) fail(EXPV_MI_ARGUMENT_ERROR, "host_taylor_theta: null output");
+    *theta = taylor_theta(precision, m);
+  });
+}
+int expv_mi_host_taylor_params(int precision, double alpha, int *m, int64_t *s) {
+  return guarded(nullptr, [&] {
+    if (!m || !s) fail(EXPV_MI_ARGUMENT_ERROR, "host_taylor_params: null output");
+    taylor_params(precision, alpha, m, s);
+  });
+}
+
 // ------------------------------------------------------------------ time stepping -----------
 void expv_mi_timestep_opts_default(expv_mi_timestep_opts *o) {
   std::memset(o, 0, sizeof(*o));

@@ -561,6 +561,26 @@ const void *dense_phi_run(Ctx *ctx, int dtype, int64_t n, int k, const void *A_d
                           int64_t info[8]);
 int dense_phi_max_k();
 
+// ---- expv_taylor.hip ----------------------------------------------------------------------
+// exp(tA)b by the truncated Taylor series (no Krylov basis).  theta_m of the precision's table; (m*, s) for a given
+// alpha = |t| opnorm(A - mu I, Inf) -- host only, both fail with EXPV_MI_ARGUMENT_ERROR outside their domain.
+double taylor_theta(int precision, int m);
+void taylor_params(int precision, double alpha, int *m, int64_t *s);
+// One call in two halves, so that the caller can queue the copy of the result between them and wait once: taylor_enqueue reads
+// mu and the norm of a stored operator (one synchronisation), chooses (m*, s) and enqueues every launch; F is the result in the
+// operator's stored ordering, valid behind what is queued on the context's stream.  taylor_collect reads the stage state
+// (the second synchronisation) and fills info / dinfo as include/expv_mi.h describes them.
+struct TaylorCall {
+  DevBuf work;                    // stage state, trace partials, v (twice) and F
+  void *state = nullptr, *F = nullptr;
+  int m = 0, path = 0;
+  int64_t s = 1, launches = 0, reads = 0;
+  double alpha = 0.0, mu_re = 0.0, mu_im = 0.0;
+};
+void taylor_enqueue(Ctx *ctx, Op &op, double t_re, double t_im, const void *b_dev, int precision, int64_t max_matvecs, double opnorm,
+                    TaylorCall &tc);
+void taylor_collect(Ctx *ctx, TaylorCall &tc, int64_t info[8], double dinfo[4]);
+
 // ---- engine_drivers.hip --------------------------------------------------------------------
 void phiv_timestep_run(Ctx *ctx, Op &op, int nts, double *ts, const void *B, int64_t ldb, int ncoef, int b_loc,
                        void *U, int64_t ldu, int u_loc, const expv_mi_timestep_opts &o, TsCache *cache,

@@ -1,0 +1,493 @@
+// expv_taylor.hip -- exp(tA)b by the truncated Taylor series of Al-Mohy & Higham (SIAM J. Sci. Comput. 33, 2011): no Krylov basis,
+// no inner product, three work vectors.
+//
+//   ext/ExponentialUtilitiesStaticArraysExt.jl:124-163 of the reference (the iteration), :76-103 (m*, s), :10-73 (theta tables)
+//
+//   mu = tr(A) / n, alpha = |t| ||A - mu I||_inf, (m*, s) = argmin m ceil(alpha / theta_m);  F = v = b;  s stages of
+//       c1 = |v|_inf;  for j = 1 .. m*:  v <- (t / s)(A - mu I) v / j,  F += v,  c2 = |v|_inf,  stop when c1 + c2 <= tol |F|_inf, c1 = c2
+//       F *= exp(mu t / s),  v = F,  leave when F is not finite
+//
+// The reference takes opnorm(A, 1) and stops at N <= 50 because it has no norm estimator; here the norm is the EXACT infinity norm,
+// one pass over the rows the operator already stores (a row maximum is order-independent, and the truncation analysis holds in any
+// subordinate norm).  The stopping rule lives on the device: every term kernel folds its workgroups' maxima of |v_i| and |F_i| into
+// the stage state with integer atomic maxima (non-negative doubles order like their bit patterns: the result does not depend on
+// arrival order), the last workgroup to arrive applies the test and publishes `stopped`, and the remaining term launches of the
+// stage return at once.  The host enqueues s (m* + 1) launches and reads nothing in between.
+//
+// Traffic per term: fused kernel (SELL slots without overflow, or the general diagonal form): the operator + x gather, x_i, F read,
+// y and F written -- the operator plus four vector streams.  Everything else: mul! (operator, x, y) + one update pass over x, y, F.
+#include <cmath>
+#include <complex>
+#include <limits>
+
+#include "engine.h"
+#include "kernel_common.h"
+#include "sparse_rows.h"
+#include "taylor_theta.h"
+
+namespace expv_mi {
+namespace dev {
+
+// Stage state, 16 words of 8 bytes.  Inside a launch every word is touched by agent-scope atomics only (maxima, OR, ticket) or by
+// lane 0 of the last workgroup to arrive, through L1-bypassing loads and stores; doubles travel as their bit patterns.
+struct TaylorState {
+  unsigned long long maxv, maxf;      // running maxima of |v_i| and |F_i| over the finite-or-infinite entries
+  unsigned long long nanflags;        // bit 0 / 1: a NaN among v / F (the hardware maximum returns the other operand), bit 2: among the row sums
+  unsigned long long ticket;
+  unsigned long long stopped;         // the stage met its stopping test (or its v is zero): the rest of its term launches do nothing
+  unsigned long long ended;           // a non-finite F ended the stage loop: every later launch does nothing
+  unsigned long long c1;              // |v|_inf of the previous term
+  unsigned long long fnorm;           // |F|_inf when the last stage closed
+  unsigned long long apps, early;     // terms that entered F; stages stopped before m*
+  unsigned long long nf_stage;        // 0, or 1 + the stage (from 0) whose F was not finite
+  unsigned long long mu_re, mu_im;    // tr(A) / n
+  unsigned long long rowmax;          // max_i ( |a_ii - mu| + sum_{j != i} |a_ij| )
+  unsigned long long spare[2];
+};
+static_assert(sizeof(TaylorState) == 128, "TaylorState layout");
+
+__device__ __forceinline__ unsigned long long ts_load(const unsigned long long *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void ts_store(unsigned long long *p, unsigned long long v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double ts_loadf(const unsigned long long *p) { return __longlong_as_double((long long)ts_load(p)); }
+__device__ __forceinline__ void ts_storef(unsigned long long *p, double v) { ts_store(p, (unsigned long long)__double_as_longlong(v)); }
+
+template <int OFF>
+__device__ __forceinline__ double xor_max(double v) {      // max(v, v[lane ^ OFF]) in every lane; no NaN among the operands
+  if constexpr (OFF >= 16) {
+    double a = v, b = v;
+    rows_swap<OFF>(a, b);
+    return fmax(a, b);
+  } else {
+    return fmax(v, lane_xor<OFF>(v));
+  }
+}
+__device__ __forceinline__ double wave_max(double v) {
+  v = xor_max<32>(v);
+  v = xor_max<16>(v);
+  v = xor_max<8>(v);
+  v = xor_max<4>(v);
+  v = xor_max<2>(v);
+  return xor_max<1>(v);
+}
+
+__device__ __forceinline__ double abs_T(double v) { return fabs(v); }
+__device__ __forceinline__ double abs_T(float v) { return (double)fabsf(v); }
+__device__ __forceinline__ double abs_T(cplx v) { return hypot(v.re, v.im); }
+__device__ __forceinline__ double abs_T(cplx32 v) { return hypot((double)v.re, (double)v.im); }
+// a maximum that keeps NaN out of the operands and remembers it in `bit` of nan
+__device__ __forceinline__ void note_abs(double a, double &m, unsigned &nan, unsigned bit) {
+  if (a != a) nan |= bit;
+  else m = fmax(m, a);
+}
+
+// Every thread of every workgroup of a launch: this workgroup's maxima into the state, then one ticket.  True in the workgroup that
+// arrives last, whose lane 0 then owns the state (everything the others added was performed before their tickets).
+__device__ __forceinline__ bool taylor_arrive(TaylorState *st, double mv, double mf, unsigned nan) {
+  __shared__ double mv_s[BLOCK / 64], mf_s[BLOCK / 64];
+  __shared__ unsigned nan_s[BLOCK / 64];
+  __shared__ int last_s;
+  mv = wave_max(mv);
+  mf = wave_max(mf);
+  nan = (__any((int)(nan & 1u)) ? 1u : 0u) | (__any((int)(nan & 2u)) ? 2u : 0u) | (__any((int)(nan & 4u)) ? 4u : 0u);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { mv_s[wave] = mv; mf_s[wave] = mf; nan_s[wave] = nan; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < BLOCK / 64; ++w) { mv = fmax(mv, mv_s[w]); mf = fmax(mf, mf_s[w]); nan |= nan_s[w]; }
+    if (mv > 0.0) atomicMax(&st->maxv, (unsigned long long)__double_as_longlong(mv));
+    if (mf > 0.0) atomicMax(&st->maxf, (unsigned long long)__double_as_longlong(mf));
+    if (nan) atomicOr(&st->nanflags, (unsigned long long)nan);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned long long t = __hip_atomic_fetch_add(&st->ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last_s = (t == (unsigned long long)gridDim.x - 1ull);
+  }
+  __syncthreads();
+  return last_s != 0;
+}
+__device__ __forceinline__ void taylor_rearm(TaylorState *st) {
+  ts_store(&st->maxv, 0ull);
+  ts_store(&st->maxf, 0ull);
+  ts_store(&st->nanflags, 0ull);
+  ts_store(&st->ticket, 0ull);
+}
+// lane 0 of the last workgroup of a term launch: the test of the reference's loop (:153-155)
+__device__ __forceinline__ void taylor_term_test(TaylorState *st, double tol, int j, int m) {
+  const unsigned long long nan = ts_load(&st->nanflags);
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  const double c2 = (nan & 1ull) ? qnan : ts_loadf(&st->maxv);
+  const double fn = (nan & 2ull) ? qnan : ts_loadf(&st->maxf);
+  const double c1 = ts_loadf(&st->c1);
+  ts_store(&st->apps, ts_load(&st->apps) + 1ull);
+  if (c1 + c2 <= tol * fn) {
+    ts_store(&st->stopped, 1ull);
+    if (j < m) ts_store(&st->early, ts_load(&st->early) + 1ull);
+  } else {
+    ts_storef(&st->c1, c2);
+  }
+  taylor_rearm(st);
+}
+__device__ __forceinline__ bool taylor_skip(const TaylorState *st) {
+  return (ts_load(&st->stopped) | ts_load(&st->ended)) != 0ull;
+}
+
+template <class T>
+struct TaylorTermArgs {
+  SellView<T> A;                                  // SELL slots (ndiag == 0) ...
+  const T *dia_val; int64_t dia_ld; int ndiag; const int32_t *dia_off;      // ... or the general diagonal form
+  const T *x;                                     // v of the previous term
+  T *y;                                           // fused: out.  update: in (A x as mul! left it) and out
+  T *F;
+  int64_t n;
+  T c, mu;                                        // (t / s) / j and tr(A) / n
+  double tol;
+  int j, m;
+  TaylorState *st;
+};
+
+// y_i = c (sum_k a_ik x_k - mu x_i), F_i += y_i, maxima, ticket: one term of the series in one pass over the operator
+template <class T>
+__global__ __launch_bounds__(BLOCK) void k_taylor_term_fused(TaylorTermArgs<T> a) {
+  if (taylor_skip(a.st)) return;
+  constexpr int N = Pack<T>::N;
+  constexpr int SH = 64 * N;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool alx = is_al16(a.x), aly = is_al16(a.y), alf = is_al16(a.F);
+  const int64_t nsl = (a.n + SH - 1) / SH;
+  double mv = 0.0, mf = 0.0;
+  unsigned nan = 0u;
+  for (int64_t slice = (int64_t)blockIdx.x * (BLOCK / 64) + wave; slice < nsl; slice += (int64_t)gridDim.x * (BLOCK / 64)) {
+    const int64_t i = slice * SH + (int64_t)lane * N;
+    const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);      // independent of the operator: in flight with its slots
+    Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
+    Pack<T> acc;
+    if (a.ndiag > 0) dia_rows<T>(a.dia_val, a.dia_ld, a.ndiag, a.dia_off, i, a.n, a.x, acc.v);
+    else sell_rows<T>(a.A, slice, lane, a.x, acc.v);
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      ST<T>::nfma(acc.v[k], a.mu, xi.v[k]);
+      acc.v[k] = ST<T>::mul(a.c, acc.v[k]);
+      f.v[k] = ST<T>::add(f.v[k], acc.v[k]);
+      if (i + k < a.n) {      // (rows of the last pack beyond n hold what the padding slots gave: not part of the vector)
+        note_abs(abs_T(acc.v[k]), mv, nan, 1u);
+        note_abs(abs_T(f.v[k]), mf, nan, 2u);
+      }
+    }
+    st_pack_user(a.y, i, a.n, aly, acc);
+    st_pack_user(a.F, i, a.n, alf, f);
+  }
+  if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m);
+}
+
+// the same behind mul!(y, A, x): y_i = c (y_i - mu x_i), F_i += y_i, maxima, ticket
+template <class T>
+__global__ __launch_bounds__(BLOCK) void k_taylor_term_update(TaylorTermArgs<T> a) {
+  if (taylor_skip(a.st)) return;
+  constexpr int N = Pack<T>::N;
+  const bool alx = is_al16(a.x), aly = is_al16(a.y), alf = is_al16(a.F);
+  double mv = 0.0, mf = 0.0;
+  unsigned nan = 0u;
+  for (int64_t i = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * N; i < a.n; i += (int64_t)gridDim.x * BLOCK * N) {
+    const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);
+    Pack<T> y = ld_pack_user(a.y, i, a.n, aly);
+    Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      ST<T>::nfma(y.v[k], a.mu, xi.v[k]);
+      y.v[k] = ST<T>::mul(a.c, y.v[k]);
+      f.v[k] = ST<T>::add(f.v[k], y.v[k]);
+      if (i + k < a.n) {
+        note_abs(abs_T(y.v[k]), mv, nan, 1u);
+        note_abs(abs_T(f.v[k]), mf, nan, 2u);
+      }
+    }
+    st_pack_user(a.y, i, a.n, aly, y);
+    st_pack_user(a.F, i, a.n, alf, f);
+  }
+  if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m);
+}
+
+// Closes a stage (:157-159): F = eta src (scale == 0: F = src as it is), v = F, c1 = |F|_inf, the finite test, and the state of the
+// next stage.  The first launch of a call is this kernel with src = b, scale = 0 and stage = -1 (no finite test: the reference
+// looks at F only after a stage).
+template <class T>
+__global__ __launch_bounds__(BLOCK) void k_taylor_close(const T *src, T *F, T *v, int64_t n, T eta, int scale, int stage, int more,
+                                                        TaylorState *st) {
+  if (ts_load(&st->ended) != 0ull) return;
+  constexpr int N = Pack<T>::N;
+  const bool als = is_al16(src), alf = is_al16(F), alv = is_al16(v);
+  double mf = 0.0;
+  unsigned nan = 0u;
+  for (int64_t i = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * N; i < n; i += (int64_t)gridDim.x * BLOCK * N) {
+    Pack<T> f = ld_pack_user(src, i, n, als);
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      if (scale) f.v[k] = ST<T>::mul(eta, f.v[k]);
+      if (i + k < n) note_abs(abs_T(f.v[k]), mf, nan, 2u);
+    }
+    if (scale || src != F) st_pack_user(F, i, n, alf, f);
+    st_pack_user(v, i, n, alv, f);
+  }
+  if (taylor_arrive(st, 0.0, mf, nan) && threadIdx.x == 0) {
+    const double fn = (ts_load(&st->nanflags) & 2ull) ? __longlong_as_double(0x7ff8000000000000ll) : ts_loadf(&st->maxf);
+    ts_storef(&st->c1, fn);
+    ts_storef(&st->fnorm, fn);
+    const bool finite = fn < __longlong_as_double(0x7ff0000000000000ll);
+    if (stage >= 0 && !finite) {
+      ts_store(&st->ended, 1ull);
+      ts_store(&st->nf_stage, (unsigned long long)stage + 1ull);
+    }
+    // a zero vector stays zero: the stage that follows applies nothing (b = 0 costs no operator application)
+    const bool zero = fn == 0.0;
+    ts_store(&st->stopped, zero ? 1ull : 0ull);
+    if (zero && more) ts_store(&st->early, ts_load(&st->early) + 1ull);
+    taylor_rearm(st);
+  }
+}
+
+// mu = tr(A) / n and ||A - mu I||_inf of a stored operator, in two launches of one kernel over the arrays the operator keeps:
+// mode 0 sums the diagonal (per-workgroup partials, finished by the last workgroup in index order: the same bits every run) and
+// leaves mu in the state; mode 1 takes max_i (|a_ii - mu| + sum_{j != i} |a_ij|), |mu| for a row without a stored diagonal entry.
+// rp == nullptr: the dense column-major block `val` with leading dimension lda.  Repeated entries of a CSR row count one by one
+// off the diagonal (an upper bound of the summed entry) and are summed on it.
+template <class T>
+__global__ __launch_bounds__(BLOCK) void k_taylor_shift_norm(int mode, int64_t n, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                            const T *__restrict__ val, int64_t lda, double *part, TaylorState *st) {
+  __shared__ double red_s[BLOCK / 64];
+  const cplx mu = make_cplx(mode ? ts_loadf(&st->mu_re) : 0.0, mode ? ts_loadf(&st->mu_im) : 0.0);
+  double tr_re = 0.0, tr_im = 0.0, best = 0.0;
+  unsigned nan = 0u;
+  for (int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x; r < n; r += (int64_t)gridDim.x * BLOCK) {
+    double d_re = 0.0, d_im = 0.0, off = 0.0;
+    auto take = [&](T v, bool diag) {
+      if (diag) {
+        if constexpr (ST<T>::is_complex) { d_re += (double)v.re; d_im += (double)v.im; }
+        else d_re += (double)v;
+      } else if (mode) {
+        off += abs_T(v);
+      }
+    };
+    if (rp) {
+      for (int32_t k = rp[r]; k < rp[r + 1]; ++k) take(val[k], ci[k] == (int32_t)r);
+    } else if (mode) {
+      for (int64_t j = 0; j < n; ++j) take(val[r + j * lda], j == r);
+    } else {
+      take(val[r + r * lda], true);
+    }
+    tr_re += d_re;
+    tr_im += d_im;
+    if (mode) note_abs(off + hypot(d_re - mu.re, d_im - mu.im), best, nan, 4u);
+  }
+  if (mode) {
+    if (taylor_arrive(st, 0.0, best, nan) && threadIdx.x == 0) {
+      ts_store(&st->rowmax, ts_load(&st->maxf));
+      const unsigned long long nf = ts_load(&st->nanflags);
+      taylor_rearm(st);
+      ts_store(&st->nanflags, nf & 4ull);      // (read by the host, cleared by the first closing launch)
+    }
+    return;
+  }
+  const double b_re = block_sum(tr_re, red_s);
+  __syncthreads();
+  const double b_im = block_sum(tr_im, red_s);
+  if (threadIdx.x == 0) {
+    publish_f64(part + blockIdx.x, b_re);
+    publish_f64(part + MAX_GRID + blockIdx.x, b_im);
+  }
+  if (!taylor_arrive(st, 0.0, 0.0, 0u)) return;
+  double s_re = 0.0, s_im = 0.0;
+  for (int b = threadIdx.x; b < (int)gridDim.x; b += BLOCK) {
+    s_re += consume_f64(part + b);
+    s_im += consume_f64(part + MAX_GRID + b);
+  }
+  __syncthreads();
+  s_re = block_sum(s_re, red_s);
+  __syncthreads();
+  s_im = block_sum(s_im, red_s);
+  if (threadIdx.x == 0) {
+    ts_storef(&st->mu_re, s_re / (double)n);
+    ts_storef(&st->mu_im, s_im / (double)n);
+    taylor_rearm(st);
+  }
+}
+
+static int taylor_grid(int64_t n, int rows_per_block) {
+  int64_t g = (n + rows_per_block - 1) / rows_per_block;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(g, MAX_GRID));
+}
+
+}  // namespace dev
+
+// ------------------------------------------------------------------------------------------
+// parameters                                     ExponentialUtilitiesStaticArraysExt.jl:76-103
+// ------------------------------------------------------------------------------------------
+static const double *taylor_table(int precision) {
+  if (precision == 0) return TAYLOR_THETA64;
+  if (precision == 1) return TAYLOR_THETA32;
+  fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: precision must be 0 (working precision) or 1 (2^-24)");
+}
+double taylor_theta(int precision, int m) {
+  const double *th = taylor_table(precision);
+  if (m < 1 || m > TAYLOR_M_MAX) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: theta_m is tabulated for m = 1 .. 55");
+  return th[m - 1];
+}
+void taylor_params(int precision, double alpha, int *m_out, int64_t *s_out) {
+  const double *th = taylor_table(precision);
+  if (!(alpha >= 0.0) || !std::isfinite(alpha))
+    fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: alpha = |t| opnorm(A - mu I, Inf) = " + std::to_string(alpha) + " is not a finite non-negative number");
+  if (alpha == 0.0) { *m_out = 0; *s_out = 1; return; }
+  int best_m = 0;
+  double best_s = 0.0;
+  unsigned __int128 best_cost = 0;
+  for (int m = 1; m <= TAYLOR_M_MAX; ++m) {
+    const double sd = std::ceil(alpha / th[m - 1]);
+    if (!(sd < 0x1p100)) continue;      // (not a candidate: its cost is far beyond every 64-bit count)
+    const unsigned __int128 cost = (unsigned __int128)sd * (unsigned)m;
+    if (best_m == 0 || cost < best_cost) { best_m = m; best_s = sd; best_cost = cost; }      // first minimum on ties
+  }
+  if (best_m == 0 || !(best_s < 0x1p62))
+    fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: alpha = " + std::to_string(alpha) + " needs more stages than a 64-bit count holds");
+  *m_out = best_m;
+  *s_out = (int64_t)best_s;
+}
+
+// ------------------------------------------------------------------------------------------
+// the call
+// ------------------------------------------------------------------------------------------
+static inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
+template <class T> static T taylor_scalar(std::complex<double> z) {
+  if constexpr (ST<T>::is_complex) { T r; r.re = (typename ST<T>::real_t)z.real(); r.im = (typename ST<T>::real_t)z.imag(); return r; }
+  else return (T)z.real();
+}
+
+template <class T>
+static void taylor_enqueue_T(Ctx *c, Op &op, std::complex<double> t, const void *b_dev, int precision, int64_t max_matvecs, double opnorm,
+                             TaylorCall &tc) {
+  hipStream_t s = c->stream;
+  const int64_t n = op.n;
+  const size_t vbytes = up16((size_t)n * sizeof(T)) + 16;
+  const size_t head = sizeof(dev::TaylorState) + sizeof(double) * 2 * dev::MAX_GRID;
+  tc.work.take_from(c, head + 3 * vbytes);
+  char *base = tc.work.as<char>();
+  dev::TaylorState *st = reinterpret_cast<dev::TaylorState *>(base);
+  double *part = reinterpret_cast<double *>(base + sizeof(dev::TaylorState));
+  T *V[2] = {reinterpret_cast<T *>(base + head), reinterpret_cast<T *>(base + head + vbytes)};
+  T *F = reinterpret_cast<T *>(base + head + 2 * vbytes);
+  tc.state = st;
+  tc.F = F;
+  HIPCHECK(hipMemsetAsync(st, 0, sizeof(dev::TaylorState), s));
+
+  // shift and norm
+  std::complex<double> mu(0.0, 0.0);
+  double anorm = opnorm;
+  if (op.kind != OP_CALLBACK) {
+    const bool dense = op.kind == OP_DENSE;
+    if (!dense && !(op.rowptr.p && (op.nnz == 0 || (op.col.p && op.val.p)))) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: sparse operator without its CSR arrays");
+    const int g = dev::taylor_grid(n, dev::BLOCK);
+    for (int mode = 0; mode < 2; ++mode) {
+      ProfScope ps(c, EXPV_MI_K_LINCOMB);
+      hipLaunchKernelGGL(dev::k_taylor_shift_norm<T>, dim3(g), dim3(dev::BLOCK), 0, s, mode, n, dense ? nullptr : op.rowptr.as<int32_t>(),
+                         dense ? nullptr : op.col.as<int32_t>(), dense ? reinterpret_cast<const T *>(op.dense_ptr) : op.val.as<T>(),
+                         dense ? op.lda : (int64_t)0, part, st);
+    }
+    dev::TaylorState h;
+    HIPCHECK(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    ++tc.reads;
+    auto f64 = [](unsigned long long u) { double d; std::memcpy(&d, &u, 8); return d; };
+    mu = std::complex<double>(f64(h.mu_re), f64(h.mu_im));
+    anorm = (h.nanflags & 4ull) ? std::numeric_limits<double>::quiet_NaN() : f64(h.rowmax);
+  }
+  tc.mu_re = mu.real();
+  tc.mu_im = mu.imag();
+  tc.alpha = std::abs(t) * anorm;
+  if (std::abs(t) == 0.0 || anorm == 0.0) tc.alpha = 0.0;      // (0 * Inf: t = 0 returns b whatever A holds)
+  const int table = (precision == 1 || dtype_is_32bit(op.dtype)) ? 1 : 0;      // precision 0: the working precision of the operator's real type
+  taylor_params(table, tc.alpha, &tc.m, &tc.s);
+  const int m = tc.m;
+  const int64_t ns = tc.s;
+  if (max_matvecs > 0 && (unsigned __int128)ns * (unsigned)m > (unsigned __int128)max_matvecs)
+    fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: alpha = " + std::to_string(tc.alpha) + " needs m* = " + std::to_string(m) + " terms in each of s = " +
+                                     std::to_string(ns) + " stages, more than max_matvecs = " + std::to_string(max_matvecs));
+  const double tol = table == 1 ? 0x1p-24 : 0x1p-53;
+
+  const bool fused = op.kind == OP_CSR && op.sell_ok && op.ovf_nseg == 0 && !op.cbf;
+  tc.path = fused ? 1 : 2;
+  dev::TaylorTermArgs<T> a{};
+  if (fused) {
+    a.A = dev::SellView<T>{op.sell_off.as<int64_t>(), op.sell_col.as<int32_t>(), op.sell_val.as<T>(), op.nslices};
+    if (op.gndiag > 0 && c->opt.dia) {
+      a.dia_val = op.gdia_ptr<T>(); a.dia_ld = op.gdia_ld; a.ndiag = op.gndiag; a.dia_off = op.gdia_off.as<int32_t>();
+    }
+  }
+  a.F = F; a.n = n; a.mu = taylor_scalar<T>(mu); a.tol = tol; a.m = m; a.st = st;
+  constexpr int SH = 64 * dev::Pack<T>::N;
+  const int g_fused = dev::taylor_grid((n + SH - 1) / SH, dev::BLOCK / 64);
+  const int g_elem = dev::taylor_grid(n, dev::BLOCK * dev::Pack<T>::N);
+  const std::complex<double> eta = std::exp(mu * t / (double)ns);
+  const bool scale = !(eta.real() == 1.0 && eta.imag() == 0.0);
+  auto close = [&](const T *src, T *v, int sc, int64_t stage) {
+    ProfScope ps(c, EXPV_MI_K_LINCOMB);
+    hipLaunchKernelGGL(dev::k_taylor_close<T>, dim3(g_elem), dim3(dev::BLOCK), 0, s, src, F, v, n, taylor_scalar<T>(eta), sc,
+                       (int)std::min<int64_t>(stage, 2147483646), (int)(stage + 1 < ns), st);
+  };
+  int p = 0;
+  close(reinterpret_cast<const T *>(b_dev), V[0], 0, -1);
+  for (int64_t stage = 0; stage < ns; ++stage) {
+    for (int j = 1; j <= m; ++j) {
+      a.x = V[p]; a.y = V[1 - p]; a.j = j;
+      a.c = taylor_scalar<T>(t / (double)ns / (double)j);
+      if (fused) {
+        ++c->cnt_opapply;
+        ProfScope ps(c, EXPV_MI_K_MATVEC);
+        hipLaunchKernelGGL(dev::k_taylor_term_fused<T>, dim3(g_fused), dim3(dev::BLOCK), 0, s, a);
+      } else {
+        op_apply_dev(op, a.x, a.y, nullptr, 0);
+        ProfScope ps(c, EXPV_MI_K_LINCOMB);
+        hipLaunchKernelGGL(dev::k_taylor_term_update<T>, dim3(g_elem), dim3(dev::BLOCK), 0, s, a);
+      }
+      ++tc.launches;
+      p ^= 1;
+    }
+    close(F, V[p], scale ? 1 : 0, stage);
+  }
+  HIPCHECK(hipGetLastError());
+}
+
+void taylor_enqueue(Ctx *c, Op &op, double t_re, double t_im, const void *b_dev, int precision, int64_t max_matvecs, double opnorm,
+                    TaylorCall &tc) {
+  c->use();
+  (void)taylor_table(precision);
+  if (t_im != 0.0 && !dtype_is_complex(op.dtype))
+    fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: a complex t needs a complex operator (a real operator with a complex result is not computed)");
+  if (op.kind == OP_CALLBACK && !(opnorm > 0.0 && std::isfinite(opnorm)))
+    fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: a matrix-free operator needs opnorm > 0, a bound on opnorm(A, Inf)");
+  try {
+    dispatch_dtype(op.dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      taylor_enqueue_T<T>(c, op, std::complex<double>(t_re, t_im), b_dev, precision, max_matvecs, opnorm, tc);
+    });
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);      // (the work vectors go back to the context: nothing may still be writing them)
+    throw;
+  }
+}
+
+void taylor_collect(Ctx *c, TaylorCall &tc, int64_t info[8], double dinfo[4]) {
+  dev::TaylorState h;
+  HIPCHECK(hipMemcpyAsync(&h, tc.state, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  ++tc.reads;
+  double fnorm;
+  std::memcpy(&fnorm, &h.fnorm, 8);
+  if (info) {
+    info[0] = tc.m; info[1] = tc.s; info[2] = (int64_t)h.apps; info[3] = (int64_t)h.early; info[4] = tc.launches; info[5] = tc.reads;
+    info[6] = tc.path; info[7] = (int64_t)h.nf_stage;
+  }
+  if (dinfo) { dinfo[0] = tc.alpha; dinfo[1] = tc.mu_re; dinfo[2] = tc.mu_im; dinfo[3] = fnorm; }
+}
+
+}  // namespace expv_mi

@@ -534,6 +534,45 @@ int expv_mi_expv_error_estimate(expv_mi_ks_t ks, expv_mi_op_t op, double t_re, d
                                 int b_loc, void *w, int w_loc, double atol, double rtol, int m,
                                 int ishermitian);
 
+/* w = exp(t A) b WITHOUT a Krylov basis: the truncated Taylor series of Al-Mohy & Higham (SIAM J. Sci. Comput. 33, 2011) -- the
+ * reference's second expv algorithm, ext/ExponentialUtilitiesStaticArraysExt.jl:124-163 (parameters :76-103, theta tables :10-73),
+ * which stops at N <= 50 for want of a norm estimator.  Three work vectors, no inner product, no host exponential.  All four element
+ * types; w has the operator's element type; b and w live where b_loc / w_loc say and may alias; a reordered operator gets its
+ * vectors permuted on entry and exit.  t_im != 0 needs a complex operator (EXPV_MI_ARGUMENT_ERROR otherwise).  Complete on return.
+ *   mu = tr(A) / n,  alpha = |t| opnorm(A - mu I, Inf),  (m*, s) as expv_mi_host_taylor_params gives them;  F = v = b, then s stages:
+ *       c1 = |v|_inf;  for j = 1 .. m*:  v <- (t / s) (A - mu I) v / j,  F += v,  c2 = |v|_inf,  stop the stage when
+ *       c1 + c2 <= tol |F|_inf, else c1 = c2;   F *= exp(mu t / s),  v = F;  the loop ends early when F is not finite.
+ *   - THE NORM IS THE INFINITY NORM, not the reference's 1-norm: the exact maximum absolute row sum, one pass over the rows a stored
+ *     operator already keeps on the device (a row without a stored diagonal entry contributes |mu|).  A row maximum does not depend
+ *     on summation order, and the truncation analysis holds in any subordinate norm.  Trace and norm are invariant under the
+ *     symmetric permutation of a reordered operator.  Matrix-free operators: mu = 0 and the caller passes opnorm > 0, a bound on
+ *     opnorm(A, Inf) (EXPV_MI_ARGUMENT_ERROR without one); for stored operators opnorm is ignored.
+ *   - precision 0: tol and table of the operator's real type (2^-53 for F64 / C64, 2^-24 for F32 / C32); 1: the 2^-24 table also for
+ *     F64 / C64 (the arithmetic stays double: the cheap mode for integrator tolerances); anything else EXPV_MI_ARGUMENT_ERROR.
+ *     In SINGLE arithmetic the series loses accuracy through its hump: the rounding error is about eps32 e^(alpha / s), and the
+ *     2^-24 table allows alpha / s up to 13.4 (-i Laplacian, ComplexF32, alpha / s = 10: 3e-4; typical cases 2e-7 .. 6e-7).  That is
+ *     the reference's behaviour for Float32 and is kept: no cap on alpha / s.
+ *   - Only the first branch of the reference's parameter search is built (alpha for every p: valid, conservative); the power-norm
+ *     refinement needs products with A'.  max_matvecs > 0 and m* s > max_matvecs: EXPV_MI_ARGUMENT_ERROR naming alpha, m*, s;
+ *     nothing is computed, w is untouched.  A non-finite alpha is an EXPV_MI_ARGUMENT_ERROR too.
+ *   - The stopping rule is decided on the device: the host enqueues s (m* + 1) launches and reads nothing in between; the launches
+ *     of a stopped stage return at once.  The maxima are order-independent: the same inputs give the same bits.
+ *   - Non-finite data is not an error: status OK, the non-finite w is returned.  t = 0 or alpha = 0 returns exp(mu t) b (b bit for
+ *     bit when that factor is 1); b = 0 returns 0 after no application; n = 0 does nothing.
+ * info (may be NULL): [0] m*, [1] s, [2] operator applications whose term entered F, [3] stages stopped before m*, [4] term launches
+ * enqueued, [5] stream synchronisations that waited for device-to-host data (<= 2: mu / alpha, and the final state together with a
+ * host w), [6] 1 = fused term kernel (SELL slots without overflow entries, or the general diagonal form), 2 = mul! + update kernel,
+ * [7] 0, or 1 + the stage (from 0) at which a non-finite F ended the loop.  dinfo (may be NULL): [0] alpha, [1] Re mu, [2] Im mu,
+ * [3] |F|_inf when the last stage closed. */
+int expv_mi_expv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc, void *w, int w_loc,
+                        int precision, int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4]);
+/* Host only: theta_m (m = 1 .. 55) of the table of `precision` (0: tol = 2^-53, 1: tol = 2^-24) -- the positive root of
+ * h~_m(x) = tol x, h~_m(x) = (-1)^m log(e^x T_m(-x)), below the first real zero of T_m(-x) (tools/expv_taylor_theta.py). */
+int expv_mi_host_taylor_theta(int precision, int m, double *theta);
+/* Host only: m* = argmin over 1 <= m <= 55 of m ceil(alpha / theta_m) (the first minimum on ties), s = ceil(alpha / theta_m*);
+ * alpha = 0 gives (0, 1); a negative, NaN or infinite alpha EXPV_MI_ARGUMENT_ERROR (message: expv_mi_last_error(NULL)). */
+int expv_mi_host_taylor_params(int precision, double alpha, int *m, int64_t *s);
+
 /* ------------------------------------------------------------------ time stepping ---- */
 typedef void (*expv_mi_print_fn)(const char *line, void *user);
 typedef struct {

@@ -667,6 +667,21 @@ function expv(t::Tt, Ks::MIKs{T, U}; expmethod = nothing, kwargs...) where {Tt, 
     expv!(w, t, Ks; kwargs...)
 end
 
+# ---- exp(tA)b without a Krylov basis: truncated Taylor series               (ext/ExponentialUtilitiesStaticArraysExt.jl:124-163) ----
+# The reference has this algorithm for SMatrix, N <= 50, only (it lacks a norm estimator); names of their own, so that nothing here
+# meets the reference's expv methods.  precision: 0 = working precision of real(T), 1 = the 2^-24 table in double arithmetic;
+# opnorm: a bound on opnorm(A, Inf), matrix-free operators only.  A complex t needs a complex operator.
+function expv_taylor!(w::MIVector{T}, t::Number, A::MIOperator{T}, b::MIVector{T}; precision::Integer = 0, max_matvecs::Integer = 0,
+                      opnorm = nothing) where {T}
+    length(w) == length(b) == size(A, 1) || throw(DimensionMismatch("length(w), length(b) and size(A, 1) must agree"))
+    check(ccall((:expv_mi_expv_taylor, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Int64, Cdouble, Ptr{Int64}, Ptr{Cdouble}),
+                ctx().h, A.h, real(t), imag(t), b.ptr, DEVICE, w.ptr, DEVICE, precision, max_matvecs,
+                opnorm === nothing ? 0.0 : Float64(opnorm), C_NULL, C_NULL), ctx().h)
+    w
+end
+expv_taylor(t::Number, A::MIOperator{T}, b::MIVector{T}; kw...) where {T} = expv_taylor!(similar(b, T, (length(b),)), t, A, b; kw...)
+
 # ---- error-estimate mode (Hermitian only)                                          (src/krylov_phiv_error_estimate.jl) ----
 struct MISubspaceCache end                                                     # stands in for StegrCache: the library owns the scratch
 get_subspace_cache(Ks::MIKs{T, U}) where {T, U <: Real} = MISubspaceCache()
