@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("EXPV_MI_LIB") or os.path.join(HERE, "libexpv_mi.so") 
 
 F64, C64, F32, C32 = 0, 1, 2, 3
 HOST, DEVICE = 0, 1
+BLOCK_COL_MAJOR, BLOCK_ROW_MAJOR = 0, 1      # EXPV_MI_BLOCK_*: element (i, k) at [i + k * ld] / at [i * ld + k]
 BSR_BLOCK_ROW_MAJOR, BSR_BLOCK_COL_MAJOR, BSR_COMPRESSED_COLS = 0, 1, 2      # layout bits of expv_mi_op_create_bsr_loc
 DIA_ALIGN_COL, DIA_ALIGN_ROW, DIA_ALIGN_START = 0, 1, 2                      # align of expv_mi_op_create_dia_loc
 ORTHO_AUTO, ORTHO_MGS, ORTHO_LOWSYNC, ORTHO_PIPELINED = 0, 1, 2, 3
@@ -129,6 +130,7 @@ PROTOTYPES = {
     "expv_mi_expv": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, C.POINTER(ArnoldiOpts), C.POINTER(ExpvStats)]),
     "expv_mi_expv_error_estimate": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _d, _d, _i, _i]),
     "expv_mi_expv_taylor": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, _i64, _d, _pi64, _pd]),
+    "expv_mi_expv_taylor_block": (_i, [_vp, _vp, _d, _d, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i, _i, _i64, _d, _pi64, _pd, _pi64, _pd]),
     "expv_mi_host_taylor_theta": (_i, [_i, _i, _pd]),
     "expv_mi_host_taylor_params": (_i, [_i, _d, _pi, _pi64]),
     "expv_mi_timestep_opts_default": (None, [C.POINTER(TimestepOpts)]),

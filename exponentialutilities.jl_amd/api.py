@@ -32,7 +32,7 @@ __all__ = [
     "phiv_timestep_", "kiops", "timestep_caches", "expv_batch", "expv_batch_multi", "RcclComm", "rccl_available", "rccl_unique_id", "ExpvMIError", "DimensionMismatch", "host_expm",
     "exponential", "exponential_", "mul_", "phi", "phi_", "balance_", "host_gebal",
     "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_dia_pattern", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
-    "expv_taylor", "expv_taylor_", "host_taylor_theta", "host_taylor_params",
+    "expv_taylor", "expv_taylor_", "expv_taylor_block", "expv_taylor_block_", "host_taylor_theta", "host_taylor_params",
 ]
 
 ExpvMIError = L.ExpvMIError
@@ -1484,6 +1484,150 @@ def expv_taylor(t, A, b, *, precision=None, max_matvecs=0, opnorm=None, return_i
     else:
         w = _empty_like(b, (b.shape[0],), T)
     return expv_taylor_(w, t, op, b, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
+
+
+_TAYLOR_BLOCK_INFO = ("m", "s", "applications_total", "worked_launches", "launches", "host_reads", "path", "nonfinite_columns")
+
+
+def _block_layout(n, p, s0, s1):
+    """(layout, ld) of an n x p block whose element (i, k) lies s0 * i + s1 * k elements from the first, or None when neither
+    dimension has a unit stride (or the other one's stride is shorter than a row / column)"""
+    if n == 0 or p == 0:      # nothing to address
+        return L.BLOCK_ROW_MAJOR, max(p, 1)
+    if s1 == 1 and (n <= 1 or s0 >= p):
+        return L.BLOCK_ROW_MAJOR, max(s0 if n > 1 else p, p, 1)
+    if s0 == 1 and (p <= 1 or s1 >= n):
+        return L.BLOCK_COL_MAJOR, max(s1 if p > 1 else n, n, 1)
+    if p <= 1 and s0 >= 1:      # one column at a row stride
+        return L.BLOCK_ROW_MAJOR, s0
+    if n <= 1 and s1 >= 1:
+        return L.BLOCK_COL_MAJOR, s1
+    return None
+
+
+class _BlockArg:
+    """A caller's 2-D block for expv_mi_expv_taylor_block: (pointer, loc, leading dimension, layout) of the array AS IT LIES in
+    memory -- a C-ordered numpy array or a contiguous torch (n, p) tensor goes in as ROW_MAJOR, nothing is transposed.  An input of
+    another element type, or one without a unit stride, is copied; an output like that is computed into a copy and written back
+    (numpy) or refused (torch)."""
+
+    def __init__(self, x, dtype, writable=False):
+        self.dtype = np.dtype(dtype)
+        self.back = None
+        if isinstance(x, DeviceArray):
+            if x.dtype != self.dtype:
+                raise TypeError(f"device array has dtype {x.dtype}, need {self.dtype}")
+            if x.ndim != 2:
+                raise DimensionMismatch("expv_taylor_block takes a 2-D block (expv_taylor takes a vector)")
+            self.ptr, self.loc, self.shape, self.keep = x.ptr, L.DEVICE, x.shape, x
+            self.layout, self.ld = L.BLOCK_COL_MAJOR, max(x.shape[0], 1)
+            return
+        if _is_torch(x) and x.is_cuda:
+            import torch
+            if x.dim() != 2:
+                raise DimensionMismatch("expv_taylor_block takes a 2-D block (expv_taylor takes a vector)")
+            want = _torch_dtype(self.dtype)
+            if x.dtype != want:
+                if writable:
+                    raise TypeError(f"output tensor must be {want}")
+                x = x.to(want)
+            n, p = x.shape
+            lay = _block_layout(n, p, x.stride(0), x.stride(1))
+            if lay is None:
+                if writable:
+                    raise TypeError("output block needs a unit stride along one dimension")
+                x = x.contiguous()
+                lay = _block_layout(n, p, x.stride(0), x.stride(1))
+            self.layout, self.ld = lay
+            st = torch.cuda.current_stream(x.device)      # (see _Arg: the library works on its own stream)
+            if not st.query():
+                st.synchronize()
+            self.ptr, self.loc, self.shape, self.keep = x.data_ptr(), L.DEVICE, (int(n), int(p)), x
+            return
+        a = np.asarray(_host_view(x))
+        if a.ndim != 2:
+            raise DimensionMismatch("expv_taylor_block takes a 2-D block (expv_taylor takes a vector)")
+        n, p = a.shape
+        isz = self.dtype.itemsize
+
+        def lay_of(a):
+            if a.dtype != self.dtype or a.strides[0] % isz or a.strides[1] % isz:
+                return None
+            return _block_layout(n, p, a.strides[0] // isz, a.strides[1] // isz)
+        lay = lay_of(a)
+        if lay is None:
+            order = "C" if a.flags.c_contiguous else "F"
+            if writable:
+                self.back = a
+                a = np.empty(a.shape, dtype=self.dtype, order=order)
+            else:
+                a = np.array(a, dtype=self.dtype, order=order)
+            lay = lay_of(a)
+        self.layout, self.ld = lay
+        self.ptr, self.loc, self.shape, self.keep, self.host = a.ctypes.data, L.HOST, (int(n), int(p)), a, a
+
+    def finish(self):
+        if self.back is not None:
+            if np.iscomplexobj(self.host) and not np.iscomplexobj(self.back):
+                raise TypeError("InexactError: complex result into a real array")
+            self.back[...] = self.host
+
+
+def expv_taylor_block_(W, t, A, B, *, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """W <- exp(t A) B for an n x p block B by the truncated Taylor series (expv_mi_expv_taylor_block): p independent problems of
+    expv_taylor_ that share every pass over the operator.  Column k of W is bit for bit ``expv_taylor(t, A, B[:, k])``.  ``B`` /
+    ``W``: 2-D numpy arrays (either order, or a view with one unit stride), torch tensors (either side; a contiguous (n, p) tensor
+    goes in row-major as it is) or DeviceArray; W may be B.  ``precision``, ``max_matvecs`` (compared with m* s, the cost of one
+    column), ``opnorm`` and ``t`` as in expv_taylor_.  Operators with a fused term kernel run in panels of 8 columns; a column that
+    has stopped is masked but keeps being streamed until the last column of its panel stops.  ``return_info``: also return the
+    dictionary kept in ``expv_taylor_block.last_info``: m, s, applications_total, worked_launches, launches, host_reads, path
+    (1 block kernel / 2 column by column), nonfinite_columns, alpha, mu, normF_max and the per-column lists applications,
+    early_stages, nonfinite_stage, normF."""
+    tr, ti, _ = _t_parts(t)
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(B))
+    opT = _as_operator(op, T)
+    ba, wa = _BlockArg(B, T), _BlockArg(W, T, writable=True)      # (W is B resolves to the same pointer, ld and layout)
+    n = opT.shape[0]
+    if ba.shape[0] != n:
+        raise DimensionMismatch(f"size(B,1) [{ba.shape[0]}] == size(A,1) [{n}] doesn't hold")
+    if wa.shape != ba.shape:
+        raise DimensionMismatch(f"size(W) [{wa.shape}] == size(B) [{ba.shape}] doesn't hold")
+    p = ba.shape[1]
+    info, dinfo = (C.c_int64 * 8)(), (C.c_double * 4)()
+    cinfo, cnorm = (C.c_int64 * max(3 * p, 1))(), (C.c_double * max(p, 1))()
+    _check(L.load().expv_mi_expv_taylor_block(opT.ctx._h, opT._h, tr, ti, ba.ptr, ba.ld, p, ba.layout, ba.loc, wa.ptr, wa.ld, wa.layout,
+                                              wa.loc, int(precision or 0), int(max_matvecs), 0.0 if opnorm is None else float(opnorm),
+                                              info, dinfo, cinfo, cnorm), opT.ctx._h)
+    wa.finish()
+    d = dict(zip(_TAYLOR_BLOCK_INFO, (int(v) for v in info)))
+    d.update(alpha=float(dinfo[0]), mu=complex(dinfo[1], dinfo[2]) if T.kind == "c" else float(dinfo[1]), normF_max=float(dinfo[3]),
+             applications=[int(cinfo[3 * k]) for k in range(p)], early_stages=[int(cinfo[3 * k + 1]) for k in range(p)],
+             nonfinite_stage=[int(cinfo[3 * k + 2]) for k in range(p)], normF=[float(cnorm[k]) for k in range(p)])
+    expv_taylor_block.last_info = d
+    return (W, d) if return_info else W
+
+
+def expv_taylor_block(t, A, B, *, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """exp(t A) B for an n x p block (see expv_taylor_block_): the result lives where ``B`` does, in B's memory order, and has the
+    element type the device worked in."""
+    if len(B.shape) != 2:
+        raise DimensionMismatch("expv_taylor_block takes a 2-D block (expv_taylor takes a vector)")
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(B))
+    shape = (int(B.shape[0]), int(B.shape[1]))
+    if isinstance(B, DeviceArray):
+        W = DeviceArray(shape, T, B.ctx)
+    elif _is_torch(B):
+        import torch
+        rowmajor = B.stride(1) == 1 or B.stride(0) != 1
+        W = (torch.empty(shape, dtype=_torch_dtype(T), device=B.device) if rowmajor
+             else torch.empty((shape[1], shape[0]), dtype=_torch_dtype(T), device=B.device).t())
+    else:
+        Bn = np.asarray(B)
+        W = np.empty(shape, dtype=T, order="F" if (Bn.flags.f_contiguous and not Bn.flags.c_contiguous) or
+                     (not Bn.flags.c_contiguous and Bn.strides[0] == Bn.itemsize) else "C")
+    return expv_taylor_block_(W, t, op, B, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
 
 
 def host_taylor_theta(m, precision=0):

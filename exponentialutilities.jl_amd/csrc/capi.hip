@@ -2796,6 +2796,42 @@ int expv_mi_expv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double 
     }
   });
 }
+int expv_mi_expv_taylor_block(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *B, int64_t ldb, int ncols,
+                              int b_layout, int b_loc, void *W, int64_t ldw, int w_layout, int w_loc, int precision,
+                              int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4], int64_t *col_info,
+                              double *col_normF) {
+  return guarded(ctx, [&] {
+    if (info) std::fill(info, info + 8, (int64_t)0);
+    if (dinfo) std::fill(dinfo, dinfo + 4, 0.0);
+    if (!ctx || !op) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_block: null context / operator");
+    if (ncols < 0) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_block: ncols = " + std::to_string(ncols) + " is negative");
+    if ((b_loc != EXPV_MI_HOST && b_loc != EXPV_MI_DEVICE) || (w_loc != EXPV_MI_HOST && w_loc != EXPV_MI_DEVICE))
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_block: unknown loc");
+    auto known = [](int l) { return l == EXPV_MI_BLOCK_COL_MAJOR || l == EXPV_MI_BLOCK_ROW_MAJOR; };
+    if (!known(b_layout) || !known(w_layout)) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_block: unknown layout (0 = column-major, 1 = row-major)");
+    const int64_t n = op->n;
+    if (n == 0 || ncols == 0) return;
+    auto ld_min = [&](int layout) { return layout == EXPV_MI_BLOCK_COL_MAJOR ? n : (int64_t)ncols; };
+    if (ldb < ld_min(b_layout) || ldw < ld_min(w_layout))
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_block: leading dimension too small (ldb = " + std::to_string(ldb) + ", ldw = " + std::to_string(ldw) +
+                                       " for an " + std::to_string(n) + " x " + std::to_string(ncols) + " block)");
+    if (!B || !W) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_block: null pointer");
+    if (b_loc == w_loc && !(B == W && ldb == ldw && b_layout == w_layout)) {
+      const size_t esz = dtype_size(op->dtype);
+      auto extent = [&](int layout, int64_t ld) {      // bytes from the first to one past the last element of the block
+        return (size_t)(layout == EXPV_MI_BLOCK_COL_MAJOR ? (ncols - 1) * ld + n : (n - 1) * ld + ncols) * esz;
+      };
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), w0 = reinterpret_cast<uintptr_t>(W);
+      if (b0 < w0 + extent(w_layout, ldw) && w0 < b0 + extent(b_layout, ldb))
+        fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_block: W overlaps B without being B (same pointer, leading dimension and layout)");
+    }
+    for (int k = 0; col_info && k < 3 * ncols; ++k) col_info[k] = 0;
+    for (int k = 0; col_normF && k < ncols; ++k) col_normF[k] = 0.0;
+    ctx->use();
+    taylor_block_run(ctx, *op, t_re, t_im, B, ldb, ncols, b_layout, b_loc, W, ldw, w_layout, w_loc, precision, max_matvecs, opnorm, info, dinfo,
+                     col_info, col_normF);
+  });
+}
 int expv_mi_host_taylor_theta(int precision, int m, double *theta) {
   return guarded(nullptr, [&] {
     if (!theta) fail(EXPV_MI_ARGUMENT_ERROR, "host_taylor_theta: null output");

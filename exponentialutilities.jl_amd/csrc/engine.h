@@ -575,11 +575,25 @@ struct TaylorCall {
   void *state = nullptr, *F = nullptr;
   int m = 0, path = 0;
   int64_t s = 1, launches = 0, reads = 0;
-  double alpha = 0.0, mu_re = 0.0, mu_im = 0.0;
+  double alpha = 0.0, mu_re = 0.0, mu_im = 0.0, tol = 0.0;
 };
 void taylor_enqueue(Ctx *ctx, Op &op, double t_re, double t_im, const void *b_dev, int precision, int64_t max_matvecs, double opnorm,
                     TaylorCall &tc);
 void taylor_collect(Ctx *ctx, TaylorCall &tc, int64_t info[8], double dinfo[4]);
+// The two parts of taylor_enqueue, for a caller that runs several vectors behind one plan (expv_taylor_block.hip).
+// taylor_shift_plan: the argument checks, mu / alpha (the one blocking read of a stored operator) and (m*, s) into tc; `head` is
+// taylor_head_bytes() of device memory whose first 128 bytes are a stage state, ready for taylor_run afterwards.  taylor_run: every
+// launch of one vector's series; `state` is `head` or 128 zeroed bytes, v0 / v1 / F hold n elements each, b_dev may be F.
+size_t taylor_head_bytes();
+void taylor_shift_plan(Ctx *ctx, Op &op, double t_re, double t_im, int precision, int64_t max_matvecs, double opnorm, void *head,
+                       TaylorCall &tc);
+void taylor_run(Ctx *ctx, Op &op, double t_re, double t_im, const void *b_dev, void *state, void *v0, void *v1, void *F, TaylorCall &tc);
+
+// ---- expv_taylor_block.hip ------------------------------------------------------------------
+// exp(tA)B for an n x ncols block (include/expv_mi.h: expv_mi_expv_taylor_block); the arguments have been checked by the caller.
+void taylor_block_run(Ctx *ctx, Op &op, double t_re, double t_im, const void *B, int64_t ldb, int ncols, int b_layout, int b_loc, void *W,
+                      int64_t ldw, int w_layout, int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[8],
+                      double dinfo[4], int64_t *col_info, double *col_normF);
 
 // ---- engine_drivers.hip --------------------------------------------------------------------
 void phiv_timestep_run(Ctx *ctx, Op &op, int nts, double *ts, const void *B, int64_t ldb, int ncoef, int b_loc,

@@ -23,66 +23,13 @@
 #include "engine.h"
 #include "kernel_common.h"
 #include "sparse_rows.h"
+#include "taylor_state.h"
 #include "taylor_theta.h"
 
 namespace expv_mi {
 namespace dev {
 
-// Stage state, 16 words of 8 bytes.  Inside a launch every word is touched by agent-scope atomics only (maxima, OR, ticket) or by
-// lane 0 of the last workgroup to arrive, through L1-bypassing loads and stores; doubles travel as their bit patterns.
-struct TaylorState {
-  unsigned long long maxv, maxf;      // running maxima of |v_i| and |F_i| over the finite-or-infinite entries
-  unsigned long long nanflags;        // bit 0 / 1: a NaN among v / F (the hardware maximum returns the other operand), bit 2: among the row sums
-  unsigned long long ticket;
-  unsigned long long stopped;         // the stage met its stopping test (or its v is zero): the rest of its term launches do nothing
-  unsigned long long ended;           // a non-finite F ended the stage loop: every later launch does nothing
-  unsigned long long c1;              // |v|_inf of the previous term
-  unsigned long long fnorm;           // |F|_inf when the last stage closed
-  unsigned long long apps, early;     // terms that entered F; stages stopped before m*
-  unsigned long long nf_stage;        // 0, or 1 + the stage (from 0) whose F was not finite
-  unsigned long long mu_re, mu_im;    // tr(A) / n
-  unsigned long long rowmax;          // max_i ( |a_ii - mu| + sum_{j != i} |a_ij| )
-  unsigned long long spare[2];
-};
-static_assert(sizeof(TaylorState) == 128, "TaylorState layout");
-
-__device__ __forceinline__ unsigned long long ts_load(const unsigned long long *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void ts_store(unsigned long long *p, unsigned long long v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ts_loadf(const unsigned long long *p) { return __longlong_as_double((long long)ts_load(p)); }
-__device__ __forceinline__ void ts_storef(unsigned long long *p, double v) { ts_store(p, (unsigned long long)__double_as_longlong(v)); }
-
-template <int OFF>
-__device__ __forceinline__ double xor_max(double v) {      // max(v, v[lane ^ OFF]) in every lane; no NaN among the operands
-  if constexpr (OFF >= 16) {
-    double a = v, b = v;
-    rows_swap<OFF>(a, b);
-    return fmax(a, b);
-  } else {
-    return fmax(v, lane_xor<OFF>(v));
-  }
-}
-__device__ __forceinline__ double wave_max(double v) {
-  v = xor_max<32>(v);
-  v = xor_max<16>(v);
-  v = xor_max<8>(v);
-  v = xor_max<4>(v);
-  v = xor_max<2>(v);
-  return xor_max<1>(v);
-}
-
-__device__ __forceinline__ double abs_T(double v) { return fabs(v); }
-__device__ __forceinline__ double abs_T(float v) { return (double)fabsf(v); }
-__device__ __forceinline__ double abs_T(cplx v) { return hypot(v.re, v.im); }
-__device__ __forceinline__ double abs_T(cplx32 v) { return hypot((double)v.re, (double)v.im); }
-// a maximum that keeps NaN out of the operands and remembers it in `bit` of nan
-__device__ __forceinline__ void note_abs(double a, double &m, unsigned &nan, unsigned bit) {
-  if (a != a) nan |= bit;
-  else m = fmax(m, a);
-}
+// (the stage state TaylorState and the small helpers shared with the block kernels: taylor_state.h)
 
 // Every thread of every workgroup of a launch: this workgroup's maxima into the state, then one ticket.  True in the workgroup that
 // arrives last, whose lane 0 then owns the state (everything the others added was performed before their tickets).
@@ -358,26 +305,18 @@ void taylor_params(int precision, double alpha, int *m_out, int64_t *s_out) {
 // the call
 // ------------------------------------------------------------------------------------------
 static inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-template <class T> static T taylor_scalar(std::complex<double> z) {
-  if constexpr (ST<T>::is_complex) { T r; r.re = (typename ST<T>::real_t)z.real(); r.im = (typename ST<T>::real_t)z.imag(); return r; }
-  else return (T)z.real();
-}
 
+size_t taylor_head_bytes() { return sizeof(dev::TaylorState) + sizeof(double) * 2 * dev::MAX_GRID; }
+
+// What depends on A and t alone: mu, alpha (two launches and the one blocking read of a stored operator) and (m*, s).  `head`:
+// taylor_head_bytes() of device memory, zeroed here; its state block is ready for the first closing launch of a call afterwards.
 template <class T>
-static void taylor_enqueue_T(Ctx *c, Op &op, std::complex<double> t, const void *b_dev, int precision, int64_t max_matvecs, double opnorm,
-                             TaylorCall &tc) {
+static void taylor_shift_plan_T(Ctx *c, Op &op, std::complex<double> t, int precision, int64_t max_matvecs, double opnorm, void *head,
+                                TaylorCall &tc) {
   hipStream_t s = c->stream;
   const int64_t n = op.n;
-  const size_t vbytes = up16((size_t)n * sizeof(T)) + 16;
-  const size_t head = sizeof(dev::TaylorState) + sizeof(double) * 2 * dev::MAX_GRID;
-  tc.work.take_from(c, head + 3 * vbytes);
-  char *base = tc.work.as<char>();
-  dev::TaylorState *st = reinterpret_cast<dev::TaylorState *>(base);
-  double *part = reinterpret_cast<double *>(base + sizeof(dev::TaylorState));
-  T *V[2] = {reinterpret_cast<T *>(base + head), reinterpret_cast<T *>(base + head + vbytes)};
-  T *F = reinterpret_cast<T *>(base + head + 2 * vbytes);
-  tc.state = st;
-  tc.F = F;
+  dev::TaylorState *st = reinterpret_cast<dev::TaylorState *>(head);
+  double *part = reinterpret_cast<double *>(static_cast<char *>(head) + sizeof(dev::TaylorState));
   HIPCHECK(hipMemsetAsync(st, 0, sizeof(dev::TaylorState), s));
 
   // shift and norm
@@ -412,7 +351,22 @@ static void taylor_enqueue_T(Ctx *c, Op &op, std::complex<double> t, const void 
   if (max_matvecs > 0 && (unsigned __int128)ns * (unsigned)m > (unsigned __int128)max_matvecs)
     fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: alpha = " + std::to_string(tc.alpha) + " needs m* = " + std::to_string(m) + " terms in each of s = " +
                                      std::to_string(ns) + " stages, more than max_matvecs = " + std::to_string(max_matvecs));
-  const double tol = table == 1 ? 0x1p-24 : 0x1p-53;
+  tc.tol = table == 1 ? 0x1p-24 : 0x1p-53;
+}
+
+// Every launch of one vector's series behind a plan: F = v = b, then s stages.  `st` is a zeroed state block (or the one the plan
+// left); v0, v1 and F hold n elements each; b may be F itself.
+template <class T>
+static void taylor_run_T(Ctx *c, Op &op, std::complex<double> t, const void *b_dev, void *state, void *v0, void *v1, void *Fv, TaylorCall &tc) {
+  hipStream_t s = c->stream;
+  const int64_t n = op.n;
+  dev::TaylorState *st = reinterpret_cast<dev::TaylorState *>(state);
+  T *V[2] = {reinterpret_cast<T *>(v0), reinterpret_cast<T *>(v1)};
+  T *F = reinterpret_cast<T *>(Fv);
+  const std::complex<double> mu(tc.mu_re, tc.mu_im);
+  const int m = tc.m;
+  const int64_t ns = tc.s;
+  const double tol = tc.tol;
 
   const bool fused = op.kind == OP_CSR && op.sell_ok && op.ovf_nseg == 0 && !op.cbf;
   tc.path = fused ? 1 : 2;
@@ -457,19 +411,35 @@ static void taylor_enqueue_T(Ctx *c, Op &op, std::complex<double> t, const void 
   HIPCHECK(hipGetLastError());
 }
 
-void taylor_enqueue(Ctx *c, Op &op, double t_re, double t_im, const void *b_dev, int precision, int64_t max_matvecs, double opnorm,
-                    TaylorCall &tc) {
-  c->use();
+void taylor_shift_plan(Ctx *c, Op &op, double t_re, double t_im, int precision, int64_t max_matvecs, double opnorm, void *head, TaylorCall &tc) {
   (void)taylor_table(precision);
   if (t_im != 0.0 && !dtype_is_complex(op.dtype))
     fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: a complex t needs a complex operator (a real operator with a complex result is not computed)");
   if (op.kind == OP_CALLBACK && !(opnorm > 0.0 && std::isfinite(opnorm)))
     fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: a matrix-free operator needs opnorm > 0, a bound on opnorm(A, Inf)");
+  dispatch_dtype(op.dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    taylor_shift_plan_T<T>(c, op, std::complex<double>(t_re, t_im), precision, max_matvecs, opnorm, head, tc);
+  });
+}
+void taylor_run(Ctx *c, Op &op, double t_re, double t_im, const void *b_dev, void *state, void *v0, void *v1, void *F, TaylorCall &tc) {
+  dispatch_dtype(op.dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    taylor_run_T<T>(c, op, std::complex<double>(t_re, t_im), b_dev, state, v0, v1, F, tc);
+  });
+}
+
+void taylor_enqueue(Ctx *c, Op &op, double t_re, double t_im, const void *b_dev, int precision, int64_t max_matvecs, double opnorm,
+                    TaylorCall &tc) {
+  c->use();
   try {
-    dispatch_dtype(op.dtype, [&](auto tag) {
-      using T = typename decltype(tag)::type;
-      taylor_enqueue_T<T>(c, op, std::complex<double>(t_re, t_im), b_dev, precision, max_matvecs, opnorm, tc);
-    });
+    const size_t vbytes = up16((size_t)op.n * dtype_size(op.dtype)) + 16, head = taylor_head_bytes();
+    tc.work.take_from(c, head + 3 * vbytes);
+    char *base = tc.work.as<char>();
+    tc.state = base;
+    tc.F = base + head + 2 * vbytes;
+    taylor_shift_plan(c, op, t_re, t_im, precision, max_matvecs, opnorm, base, tc);
+    taylor_run(c, op, t_re, t_im, b_dev, base, base + head, base + head + vbytes, tc.F, tc);
   } catch (...) {
     (void)hipStreamSynchronize(c->stream);      // (the work vectors go back to the context: nothing may still be writing them)
     throw;

@@ -1,6 +1,6 @@
 // sparse_rows.h -- the rows of a stored sparse operator applied to a vector, one 16-byte row pack per lane (gfx950 only):
 // from the SELL-C slots or from the general DIA form.  Shared by the Krylov half-steps (fused.hip) and the truncated-Taylor term
-// kernel (expv_taylor.hip).
+// kernels (expv_taylor.hip: one vector; expv_taylor_block.hip: P interleaved columns behind the same two loops).
 #pragma once
 #include "kernel_common.h"
 
@@ -32,79 +32,111 @@ __device__ __forceinline__ void load_cols<cplx32>(const int32_t *p, int32_t *c) 
   c[1] = v.y;
 }
 
+// The two operator loops below are written once for whatever stands on the right-hand side.  X is the operand and the accumulator
+// of a lane's N rows:
+//   typename X::row_t        what one column index fetches (one element of a vector; the P adjacent values of an interleaved block)
+//   x.clear(k)               acc_k = 0
+//   x.at(c) / X::none()      the operand of column c / of a column outside the matrix
+//   x.fma(k, a, g)           acc_k += a * g, one ST<T>::fma_ per accumulated value
+// OneVector is the single right-hand side of dia_rows / sell_rows.  Q = the diagonals / slots a lane keeps in flight; the sums run in
+// ascending order whatever Q is.
+template <class T>
+struct OneVector {
+  using row_t = T;
+  const T *__restrict__ x;
+  T *acc;
+  __device__ __forceinline__ void clear(int k) { acc[k] = ST<T>::zero(); }
+  __device__ __forceinline__ T at(int64_t c) const { return x[c]; }
+  __device__ __forceinline__ static T none() { return ST<T>::zero(); }
+  __device__ __forceinline__ void fma(int k, T a, const T &g) { ST<T>::fma_(acc[k], a, g); }
+};
+
 // y-rows of one slice for this lane from the DIA form: acc[k] = sum_d val[d][r] * x[r + off[d]]  (ascending offsets =
 // ascending columns: the order of the CSR/SELL row; absent entries are explicit zeros)
-template <class T>
-__device__ __forceinline__ void dia_rows(const T *__restrict__ dval, int64_t ld, int ndiag, const int32_t *__restrict__ doff,
-                                         int64_t i, int64_t n, const T *__restrict__ x, T *acc) {
+template <class T, int Q, class X>
+__device__ __forceinline__ void dia_walk(const T *__restrict__ dval, int64_t ld, int ndiag, const int32_t *__restrict__ doff,
+                                         int64_t i, int64_t n, X &xs) {
   constexpr int N = Pack<T>::N;
+  using R = typename X::row_t;
 #pragma unroll
-  for (int k = 0; k < N; ++k) acc[k] = ST<T>::zero();
+  for (int k = 0; k < N; ++k) xs.clear(k);
   int d = 0;
-  for (; d + 4 <= ndiag; d += 4) {   // 4 diagonals in flight
-    Pack<T> v[4];
-    T xv[4][N];
+  for (; d + Q <= ndiag; d += Q) {   // Q diagonals in flight
+    Pack<T> v[Q];
+    R xv[Q][N];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < Q; ++q) {
       v[q] = *reinterpret_cast<const Pack<T> *>(dval + (int64_t)(d + q) * ld + i);
       const int64_t c0 = i + doff[d + q];
 #pragma unroll
-      for (int k = 0; k < N; ++k) xv[q][k] = (c0 + k >= 0 && c0 + k < n) ? x[c0 + k] : ST<T>::zero();
+      for (int k = 0; k < N; ++k) xv[q][k] = (c0 + k >= 0 && c0 + k < n) ? xs.at(c0 + k) : X::none();
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+    for (int q = 0; q < Q; ++q)
 #pragma unroll
-      for (int k = 0; k < N; ++k) ST<T>::fma_(acc[k], v[q].v[k], xv[q][k]);
+      for (int k = 0; k < N; ++k) xs.fma(k, v[q].v[k], xv[q][k]);
   }
   for (; d < ndiag; ++d) {
     const Pack<T> v = *reinterpret_cast<const Pack<T> *>(dval + (int64_t)d * ld + i);
     const int64_t c0 = i + doff[d];
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      const T xk = (c0 + k >= 0 && c0 + k < n) ? x[c0 + k] : ST<T>::zero();
-      ST<T>::fma_(acc[k], v.v[k], xk);
+      const R xk = (c0 + k >= 0 && c0 + k < n) ? xs.at(c0 + k) : X::none();
+      xs.fma(k, v.v[k], xk);
     }
   }
 }
+template <class T>
+__device__ __forceinline__ void dia_rows(const T *__restrict__ dval, int64_t ld, int ndiag, const int32_t *__restrict__ doff,
+                                         int64_t i, int64_t n, const T *__restrict__ x, T *acc) {
+  OneVector<T> xs{x, acc};
+  dia_walk<T, 4>(dval, ld, ndiag, doff, i, n, xs);
+}
 
 // y-rows of one slice for this lane: acc[k] = sum_slots val * x[col]
-template <class T>
-__device__ __forceinline__ void sell_rows(const SellView<T> &A, int64_t slice, int lane, const T *__restrict__ x,
-                                          T *acc) {
+template <class T, int Q, class X>
+__device__ __forceinline__ void sell_walk(const SellView<T> &A, int64_t slice, int lane, X &xs) {
   constexpr int N = Pack<T>::N;
   constexpr int SH = 64 * N;
+  using R = typename X::row_t;
   const int64_t off = A.slice_off[slice];
   const int L = (int)((A.slice_off[slice + 1] - off) / SH);
   const T *vp = A.val + off + (int64_t)lane * N;
   const int32_t *cp = A.col + off + (int64_t)lane * N;
 #pragma unroll
-  for (int k = 0; k < N; ++k) acc[k] = ST<T>::zero();
+  for (int k = 0; k < N; ++k) xs.clear(k);
   int s = 0;
-  for (; s + 4 <= L; s += 4) {  // 4 slots in flight: 4 x 16 B of values + indices, then 4N gathers
-    Pack<T> v[4];
-    int32_t c[4][N];
+  for (; s + Q <= L; s += Q) {  // Q slots in flight: Q x 16 B of values + indices, then Q N gathers
+    Pack<T> v[Q];
+    int32_t c[Q][N];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < Q; ++q) {
       v[q] = *reinterpret_cast<const Pack<T> *>(vp + (int64_t)(s + q) * SH);
       load_cols<T>(cp + (int64_t)(s + q) * SH, c[q]);
     }
-    T xv[4][N];
+    R xv[Q][N];
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+    for (int q = 0; q < Q; ++q)
 #pragma unroll
-      for (int k = 0; k < N; ++k) xv[q][k] = x[c[q][k]];
+      for (int k = 0; k < N; ++k) xv[q][k] = xs.at(c[q][k]);
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+    for (int q = 0; q < Q; ++q)
 #pragma unroll
-      for (int k = 0; k < N; ++k) ST<T>::fma_(acc[k], v[q].v[k], xv[q][k]);
+      for (int k = 0; k < N; ++k) xs.fma(k, v[q].v[k], xv[q][k]);
   }
   for (; s < L; ++s) {
     const Pack<T> v = *reinterpret_cast<const Pack<T> *>(vp + (int64_t)s * SH);
     int32_t c[N];
     load_cols<T>(cp + (int64_t)s * SH, c);
 #pragma unroll
-    for (int k = 0; k < N; ++k) ST<T>::fma_(acc[k], v.v[k], x[c[k]]);
+    for (int k = 0; k < N; ++k) xs.fma(k, v.v[k], xs.at(c[k]));
   }
+}
+template <class T>
+__device__ __forceinline__ void sell_rows(const SellView<T> &A, int64_t slice, int lane, const T *__restrict__ x,
+                                          T *acc) {
+  OneVector<T> xs{x, acc};
+  sell_walk<T, 4>(A, slice, lane, xs);
 }
 
 }  // namespace dev

@@ -573,6 +573,36 @@ int expv_mi_host_taylor_theta(int precision, int m, double *theta);
  * alpha = 0 gives (0, 1); a negative, NaN or infinite alpha EXPV_MI_ARGUMENT_ERROR (message: expv_mi_last_error(NULL)). */
 int expv_mi_host_taylor_params(int precision, double alpha, int *m, int64_t *s);
 
+/* W = exp(t A) B for an n x ncols block B: ncols independent problems of expv_mi_expv_taylor that share every pass over the operator.
+ * (mu, alpha, m*, s) depend on A and t alone and are computed once; every column keeps its own stopping state, and COLUMN k OF W IS BIT
+ * FOR BIT what expv_mi_expv_taylor returns for column k of B with the same operator, t and precision.
+ *   - B and W have the operator's element type and live where b_loc / w_loc say.  Layouts: */
+enum { EXPV_MI_BLOCK_COL_MAJOR = 0,   /* element (i,k) at [i + k*ld]: Julia, Fortran-order numpy */
+       EXPV_MI_BLOCK_ROW_MAJOR = 1 }; /* element (i,k) at [i*ld + k]: a contiguous torch (n,p) tensor */
+/*     Elements between the columns (rows) of a padded leading dimension are neither read nor written.  W may be B itself (same
+ *     pointer, ld and layout); any other overlap is EXPV_MI_ARGUMENT_ERROR.
+ *   - Operators with a fused term kernel (SELL slots without overflow entries, or the general diagonal form) run in panels of 8
+ *     columns (the remainder in the smallest panel of 2, 4 or 8 that holds it, padded with zero columns) on work vectors that keep a
+ *     row's values adjacent: the operator is read once per term for the whole panel, and a gathered column index is one contiguous
+ *     access.  A column that has stopped or ended is masked in the later term launches of its stage (its F is written back
+ *     unchanged) but keeps being streamed until the last column of its panel stops; a launch whose columns have all stopped returns
+ *     at once.  Every other operator (SELL with overflow entries, dense, matrix-free) runs the single-vector loop column by column.
+ *     ncols = 1 runs the single-vector loop as well.
+ *   - precision, max_matvecs (compared with m* s, the cost of ONE column), opnorm and the refusal of a complex t on a real operator
+ *     are those of expv_mi_expv_taylor, with its messages; a refused call leaves W untouched.  ncols = 0 or n = 0 does nothing;
+ *     ncols < 0, an unknown layout or loc and a leading dimension too small are EXPV_MI_ARGUMENT_ERROR "expv_taylor_block: ...",
+ *     found before any device work.  Complete on return.
+ * info (may be NULL): [0] m*, [1] s, [2] applications summed over the columns, [3] term launches that did work (did not return at
+ * once), [4] term launches enqueued, [5] stream synchronisations that waited for device-to-host data (<= 2), [6] 1 = block kernel
+ * (ncols = 1: the fused single-vector kernel), 2 = column by column through the mul! + update loop, [7] columns whose F went
+ * non-finite.  dinfo (may be NULL): as expv_mi_expv_taylor, [3] = the largest |F|_inf of a column (NaN when one is).  col_info (NULL
+ * or 3 ncols words): info[2], info[3], info[7] of the single call for column k at [3k .. 3k+2]; col_normF (NULL or ncols): its
+ * dinfo[3]. */
+int expv_mi_expv_taylor_block(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *B, int64_t ldb, int ncols,
+                              int b_layout, int b_loc, void *W, int64_t ldw, int w_layout, int w_loc, int precision,
+                              int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4], int64_t *col_info,
+                              double *col_normF);
+
 /* ------------------------------------------------------------------ time stepping ---- */
 typedef void (*expv_mi_print_fn)(const char *line, void *user);
 typedef struct {

@@ -681,6 +681,19 @@ function expv_taylor!(w::MIVector{T}, t::Number, A::MIOperator{T}, b::MIVector{T
     w
 end
 expv_taylor(t::Number, A::MIOperator{T}, b::MIVector{T}; kw...) where {T} = expv_taylor!(similar(b, T, (length(b),)), t, A, b; kw...)
+# A block of columns: size(B, 2) independent problems that share every pass over the operator; W[:, k] is bit for bit
+# expv_taylor(t, A, B[:, k]).  W may be B.  A column that has stopped is masked but streamed until its panel of 8 has stopped.
+function expv_taylor!(W::MIMatrix{T}, t::Number, A::MIOperator{T}, B::MIMatrix{T}; precision::Integer = 0, max_matvecs::Integer = 0,
+                      opnorm = nothing) where {T}
+    size(W) == size(B) && size(B, 1) == size(A, 1) || throw(DimensionMismatch("size(W), size(B) and size(A, 1) must agree"))
+    check(ccall((:expv_mi_expv_taylor_block, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Cvoid}, Int64, Cint, Cint, Cint, Int64,
+                 Cdouble, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cdouble}),
+                ctx().h, A.h, real(t), imag(t), B.ptr, ld(B), ncols(B), 0, DEVICE, W.ptr, ld(W), 0, DEVICE, precision, max_matvecs,
+                opnorm === nothing ? 0.0 : Float64(opnorm), C_NULL, C_NULL, C_NULL, C_NULL), ctx().h)
+    W
+end
+expv_taylor(t::Number, A::MIOperator{T}, B::MIMatrix{T}; kw...) where {T} = expv_taylor!(similar(B, T, size(B)), t, A, B; kw...)
 
 # ---- error-estimate mode (Hermitian only)                                          (src/krylov_phiv_error_estimate.jl) ----
 struct MISubspaceCache end                                                     # stands in for StegrCache: the library owns the scratch
