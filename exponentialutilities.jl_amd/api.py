@@ -32,7 +32,7 @@ __all__ = [
     "phiv_timestep_", "kiops", "timestep_caches", "expv_batch", "expv_batch_multi", "RcclComm", "rccl_available", "rccl_unique_id", "ExpvMIError", "DimensionMismatch", "host_expm",
     "exponential", "exponential_", "mul_", "phi", "phi_", "balance_", "host_gebal",
     "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_dia_pattern", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
-    "expv_taylor", "expv_taylor_", "expv_taylor_block", "expv_taylor_block_", "host_taylor_theta", "host_taylor_params",
+    "expv_taylor", "expv_taylor_", "expv_taylor_block", "expv_taylor_block_", "phiv_taylor", "phiv_taylor_", "host_taylor_theta", "host_taylor_params",
 ]
 
 ExpvMIError = L.ExpvMIError
@@ -1628,6 +1628,54 @@ def expv_taylor_block(t, A, B, *, precision=None, max_matvecs=0, opnorm=None, re
         W = np.empty(shape, dtype=T, order="F" if (Bn.flags.f_contiguous and not Bn.flags.c_contiguous) or
                      (not Bn.flags.c_contiguous and Bn.strides[0] == Bn.itemsize) else "C")
     return expv_taylor_block_(W, t, op, B, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
+
+
+def phiv_taylor_(w, t, A, B, *, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """w <- phi_0(tA) u_0 + t phi_1(tA) u_1 + ... + t^p phi_p(tA) u_p for B = [u_0 ... u_p] (the result of phiv_timestep(t, A, B)) by the
+    truncated Taylor series on Al-Mohy & Higham's augmented matrix (expv_mi_phiv_taylor): no Krylov basis, no host exponential, three
+    work vectors of n elements.  ``B``: an n x (p + 1) block, p <= 8, numpy (either order), torch (either side) or DeviceArray, taken
+    as it lies in memory; ``w``: a vector as in expv_taylor_, which may be column 0 of B.  ``precision``, ``max_matvecs``, ``opnorm``
+    and ``t`` as in expv_taylor_.  One column is expv_taylor_ bit for bit.  ``return_info``: also return the dictionary kept in
+    ``phiv_taylor.last_info``: the keys of expv_taylor_ plus ``nu`` (the scaling of the forcing columns behind alpha) and ``U``
+    (max |u_k[i]|, k >= 1)."""
+    tr, ti, _ = _t_parts(t)
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(B))
+    opT = _as_operator(op, T)
+    ba, wa = _BlockArg(B, T), _Arg(_host_view(w), T, writable=True)
+    n = opT.shape[0]
+    if ba.shape[0] != n:
+        raise DimensionMismatch(f"size(B,1) [{ba.shape[0]}] == size(A,1) [{n}] doesn't hold")
+    if int(np.prod(wa.shape)) != n:
+        raise DimensionMismatch(f"length(w) [{int(np.prod(wa.shape))}] == size(A,1) [{n}] doesn't hold")
+    info, dinfo = (C.c_int64 * 8)(), (C.c_double * 8)()
+    _check(L.load().expv_mi_phiv_taylor(opT.ctx._h, opT._h, tr, ti, ba.ptr, ba.ld, ba.shape[1], ba.layout, ba.loc, wa.ptr, wa.loc,
+                                        int(precision or 0), int(max_matvecs), 0.0 if opnorm is None else float(opnorm), info, dinfo),
+           opT.ctx._h)
+    wa.finish()
+    d = dict(zip(_TAYLOR_INFO, (int(v) for v in info)))
+    d.update(alpha=float(dinfo[0]), mu=complex(dinfo[1], dinfo[2]) if T.kind == "c" else float(dinfo[1]), normF=float(dinfo[3]),
+             nu=float(dinfo[4]), U=float(dinfo[5]))
+    phiv_taylor.last_info = d
+    return (w, d) if return_info else w
+
+
+def phiv_taylor(t, A, B, *, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """sum_k t^k phi_k(tA) B[:, k] by the truncated Taylor series (see phiv_taylor_): a vector that lives where ``B`` does and has the
+    element type the device worked in."""
+    if len(B.shape) != 2:
+        raise DimensionMismatch("phiv_taylor takes a 2-D block B = [u_0 ... u_p]")
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(B))
+    n = int(B.shape[0])
+    if isinstance(B, DeviceArray):
+        w = DeviceArray((n,), T, B.ctx)
+    elif _is_torch(B):
+        import torch
+        w = torch.empty(n, dtype=_torch_dtype(T), device=B.device)
+    else:
+        w = np.empty(n, dtype=T)
+    return phiv_taylor_(w, t, op, B, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
 
 
 def host_taylor_theta(m, precision=0):

@@ -2832,6 +2832,53 @@ int expv_mi_expv_taylor_block(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, d
                      col_info, col_normF);
   });
 }
+int expv_mi_phiv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *B, int64_t ldb, int ncols, int b_layout,
+                        int b_loc, void *w, int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[8]) {
+  return guarded(ctx, [&] {
+    if (info) std::fill(info, info + 8, (int64_t)0);
+    if (dinfo) std::fill(dinfo, dinfo + 8, 0.0);
+    if (ncols < 1 || ncols > phiv_taylor_pmax() + 1)
+      fail(EXPV_MI_ARGUMENT_ERROR, "phiv_taylor: ncols = " + std::to_string(ncols) + " is outside 1 .. " + std::to_string(phiv_taylor_pmax() + 1) +
+                                       " (B = [u_0 ... u_p], p <= " + std::to_string(phiv_taylor_pmax()) + ")");
+    if ((b_loc != EXPV_MI_HOST && b_loc != EXPV_MI_DEVICE) || (w_loc != EXPV_MI_HOST && w_loc != EXPV_MI_DEVICE))
+      fail(EXPV_MI_ARGUMENT_ERROR, "phiv_taylor: unknown loc");
+    if (b_layout != EXPV_MI_BLOCK_COL_MAJOR && b_layout != EXPV_MI_BLOCK_ROW_MAJOR)
+      fail(EXPV_MI_ARGUMENT_ERROR, "phiv_taylor: unknown layout (0 = column-major, 1 = row-major)");
+    if (!ctx || !op) fail(EXPV_MI_ARGUMENT_ERROR, "phiv_taylor: null context / operator");
+    const int64_t n = op->n;
+    if (n == 0) return;
+    const bool colmajor = b_layout == EXPV_MI_BLOCK_COL_MAJOR;
+    if (ldb < (colmajor ? n : (int64_t)ncols))
+      fail(EXPV_MI_ARGUMENT_ERROR, "phiv_taylor: leading dimension too small (ldb = " + std::to_string(ldb) + " for an " + std::to_string(n) + " x " +
+                                       std::to_string(ncols) + " block)");
+    if (!B || !w) fail(EXPV_MI_ARGUMENT_ERROR, "phiv_taylor: null pointer");
+    if (b_loc == w_loc && ncols > 1) {      // w may be column 0; it may not reach an element of u_1 .. u_p
+      const size_t esz = dtype_size(op->dtype);
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), w0 = reinterpret_cast<uintptr_t>(w), w1 = w0 + (size_t)n * esz;
+      bool hit = false;
+      if (colmajor) {
+        for (int k = 1; k < ncols && !hit; ++k) {
+          const uintptr_t c0 = b0 + (size_t)k * (size_t)ldb * esz;
+          hit = c0 < w1 && w0 < c0 + (size_t)n * esz;
+        }
+      } else {      // row i keeps u_1 .. u_p in [i ldb + 1, i ldb + ncols): the first row that ends behind w0 decides
+        const size_t pitch = (size_t)ldb * esz;
+        const uintptr_t last = b0 + (size_t)(n - 1) * pitch + (size_t)ncols * esz;
+        if (w0 < last && b0 < w1) {
+          const uintptr_t rel = w0 > b0 ? w0 - b0 : 0;
+          for (int64_t i = (int64_t)(rel / pitch); i < n && !hit; ++i) {
+            const uintptr_t r0 = b0 + (size_t)i * pitch + esz, r1 = b0 + (size_t)i * pitch + (size_t)ncols * esz;
+            if (r0 >= w1) break;
+            hit = w0 < r1;
+          }
+        }
+      }
+      if (hit) fail(EXPV_MI_ARGUMENT_ERROR, "phiv_taylor: w overlaps a column of B other than column 0");
+    }
+    ctx->use();
+    phiv_taylor_run(ctx, *op, t_re, t_im, B, ldb, ncols, b_layout, b_loc, w, w_loc, precision, max_matvecs, opnorm, info, dinfo);
+  });
+}
 int expv_mi_host_taylor_theta(int precision, int m, double *theta) {
   return guarded(nullptr, [&] {
     if (!theta) fail(EXPV_MI_ARGUMENT_ERROR, "host_taylor_theta: null output");

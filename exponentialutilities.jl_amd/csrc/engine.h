@@ -588,12 +588,28 @@ size_t taylor_head_bytes();
 void taylor_shift_plan(Ctx *ctx, Op &op, double t_re, double t_im, int precision, int64_t max_matvecs, double opnorm, void *head,
                        TaylorCall &tc);
 void taylor_run(Ctx *ctx, Op &op, double t_re, double t_im, const void *b_dev, void *state, void *v0, void *v1, void *F, TaylorCall &tc);
+// The pieces of the plan that phiv_taylor.hip shares: the argument checks (precision, complex t on a real operator, a matrix-free
+// operator's opnorm), and (m*, s), tol and the max_matvecs refusal for the alpha in tc -- with the messages of expv_taylor.
+void taylor_check(const Op &op, double t_im, int precision, double opnorm);
+void taylor_choose(const Op &op, int precision, int64_t max_matvecs, TaylorCall &tc);
 
 // ---- expv_taylor_block.hip ------------------------------------------------------------------
 // exp(tA)B for an n x ncols block (include/expv_mi.h: expv_mi_expv_taylor_block); the arguments have been checked by the caller.
 void taylor_block_run(Ctx *ctx, Op &op, double t_re, double t_im, const void *B, int64_t ldb, int ncols, int b_layout, int b_loc, void *W,
                       int64_t ldw, int w_layout, int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[8],
                       double dinfo[4], int64_t *col_info, double *col_normF);
+
+// dst(i, k) = src(idx ? idx[i] : i, k) for the n x ncols device blocks whose element (i, k) lies rs * i + cs * k elements from the first:
+// one launch per 65535 columns, enqueued on the context's stream (a change of layout, a row permutation, or both)
+void taylor_block_copy(Ctx *ctx, Op &op, const void *src, int64_t srs, int64_t scs, void *dst, int64_t drs, int64_t dcs, const int32_t *idx,
+                       int ncols);
+
+// ---- phiv_taylor.hip ------------------------------------------------------------------------
+// w = sum_k t^k phi_k(tA) u_k for B = [u_0 ... u_p] by the same series (include/expv_mi.h: expv_mi_phiv_taylor); the arguments have
+// been checked by the caller.
+void phiv_taylor_run(Ctx *ctx, Op &op, double t_re, double t_im, const void *B, int64_t ldb, int ncols, int b_layout, int b_loc, void *w,
+                     int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[8]);
+int phiv_taylor_pmax();
 
 // ---- engine_drivers.hip --------------------------------------------------------------------
 void phiv_timestep_run(Ctx *ctx, Op &op, int nts, double *ts, const void *B, int64_t ldb, int ncoef, int b_loc,

@@ -31,69 +31,7 @@ namespace dev {
 
 // (the stage state TaylorState and the small helpers shared with the block kernels: taylor_state.h)
 
-// Every thread of every workgroup of a launch: this workgroup's maxima into the state, then one ticket.  True in the workgroup that
-// arrives last, whose lane 0 then owns the state (everything the others added was performed before their tickets).
-__device__ __forceinline__ bool taylor_arrive(TaylorState *st, double mv, double mf, unsigned nan) {
-  __shared__ double mv_s[BLOCK / 64], mf_s[BLOCK / 64];
-  __shared__ unsigned nan_s[BLOCK / 64];
-  __shared__ int last_s;
-  mv = wave_max(mv);
-  mf = wave_max(mf);
-  nan = (__any((int)(nan & 1u)) ? 1u : 0u) | (__any((int)(nan & 2u)) ? 2u : 0u) | (__any((int)(nan & 4u)) ? 4u : 0u);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { mv_s[wave] = mv; mf_s[wave] = mf; nan_s[wave] = nan; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < BLOCK / 64; ++w) { mv = fmax(mv, mv_s[w]); mf = fmax(mf, mf_s[w]); nan |= nan_s[w]; }
-    if (mv > 0.0) atomicMax(&st->maxv, (unsigned long long)__double_as_longlong(mv));
-    if (mf > 0.0) atomicMax(&st->maxf, (unsigned long long)__double_as_longlong(mf));
-    if (nan) atomicOr(&st->nanflags, (unsigned long long)nan);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long t = __hip_atomic_fetch_add(&st->ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_s = (t == (unsigned long long)gridDim.x - 1ull);
-  }
-  __syncthreads();
-  return last_s != 0;
-}
-__device__ __forceinline__ void taylor_rearm(TaylorState *st) {
-  ts_store(&st->maxv, 0ull);
-  ts_store(&st->maxf, 0ull);
-  ts_store(&st->nanflags, 0ull);
-  ts_store(&st->ticket, 0ull);
-}
-// lane 0 of the last workgroup of a term launch: the test of the reference's loop (:153-155)
-__device__ __forceinline__ void taylor_term_test(TaylorState *st, double tol, int j, int m) {
-  const unsigned long long nan = ts_load(&st->nanflags);
-  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-  const double c2 = (nan & 1ull) ? qnan : ts_loadf(&st->maxv);
-  const double fn = (nan & 2ull) ? qnan : ts_loadf(&st->maxf);
-  const double c1 = ts_loadf(&st->c1);
-  ts_store(&st->apps, ts_load(&st->apps) + 1ull);
-  if (c1 + c2 <= tol * fn) {
-    ts_store(&st->stopped, 1ull);
-    if (j < m) ts_store(&st->early, ts_load(&st->early) + 1ull);
-  } else {
-    ts_storef(&st->c1, c2);
-  }
-  taylor_rearm(st);
-}
-__device__ __forceinline__ bool taylor_skip(const TaylorState *st) {
-  return (ts_load(&st->stopped) | ts_load(&st->ended)) != 0ull;
-}
-
-template <class T>
-struct TaylorTermArgs {
-  SellView<T> A;                                  // SELL slots (ndiag == 0) ...
-  const T *dia_val; int64_t dia_ld; int ndiag; const int32_t *dia_off;      // ... or the general diagonal form
-  const T *x;                                     // v of the previous term
-  T *y;                                           // fused: out.  update: in (A x as mul! left it) and out
-  T *F;
-  int64_t n;
-  T c, mu;                                        // (t / s) / j and tr(A) / n
-  double tol;
-  int j, m;
-  TaylorState *st;
-};
+// (taylor_arrive, the stopping test, TaylorTermArgs, the closing kernel and taylor_grid are shared with phiv_taylor.hip: taylor_state.h)
 
 // y_i = c (sum_k a_ik x_k - mu x_i), F_i += y_i, maxima, ticket: one term of the series in one pass over the operator
 template <class T>
@@ -126,7 +64,7 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_term_fused(TaylorTermArgs<T> a
     st_pack_user(a.y, i, a.n, aly, acc);
     st_pack_user(a.F, i, a.n, alf, f);
   }
-  if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m);
+  if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m, 0.0);
 }
 
 // the same behind mul!(y, A, x): y_i = c (y_i - mu x_i), F_i += y_i, maxima, ticket
@@ -154,45 +92,7 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_term_update(TaylorTermArgs<T> 
     st_pack_user(a.y, i, a.n, aly, y);
     st_pack_user(a.F, i, a.n, alf, f);
   }
-  if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m);
-}
-
-// Closes a stage (:157-159): F = eta src (scale == 0: F = src as it is), v = F, c1 = |F|_inf, the finite test, and the state of the
-// next stage.  The first launch of a call is this kernel with src = b, scale = 0 and stage = -1 (no finite test: the reference
-// looks at F only after a stage).
-template <class T>
-__global__ __launch_bounds__(BLOCK) void k_taylor_close(const T *src, T *F, T *v, int64_t n, T eta, int scale, int stage, int more,
-                                                        TaylorState *st) {
-  if (ts_load(&st->ended) != 0ull) return;
-  constexpr int N = Pack<T>::N;
-  const bool als = is_al16(src), alf = is_al16(F), alv = is_al16(v);
-  double mf = 0.0;
-  unsigned nan = 0u;
-  for (int64_t i = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * N; i < n; i += (int64_t)gridDim.x * BLOCK * N) {
-    Pack<T> f = ld_pack_user(src, i, n, als);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      if (scale) f.v[k] = ST<T>::mul(eta, f.v[k]);
-      if (i + k < n) note_abs(abs_T(f.v[k]), mf, nan, 2u);
-    }
-    if (scale || src != F) st_pack_user(F, i, n, alf, f);
-    st_pack_user(v, i, n, alv, f);
-  }
-  if (taylor_arrive(st, 0.0, mf, nan) && threadIdx.x == 0) {
-    const double fn = (ts_load(&st->nanflags) & 2ull) ? __longlong_as_double(0x7ff8000000000000ll) : ts_loadf(&st->maxf);
-    ts_storef(&st->c1, fn);
-    ts_storef(&st->fnorm, fn);
-    const bool finite = fn < __longlong_as_double(0x7ff0000000000000ll);
-    if (stage >= 0 && !finite) {
-      ts_store(&st->ended, 1ull);
-      ts_store(&st->nf_stage, (unsigned long long)stage + 1ull);
-    }
-    // a zero vector stays zero: the stage that follows applies nothing (b = 0 costs no operator application)
-    const bool zero = fn == 0.0;
-    ts_store(&st->stopped, zero ? 1ull : 0ull);
-    if (zero && more) ts_store(&st->early, ts_load(&st->early) + 1ull);
-    taylor_rearm(st);
-  }
+  if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m, 0.0);
 }
 
 // mu = tr(A) / n and ||A - mu I||_inf of a stored operator, in two launches of one kernel over the arrays the operator keeps:
@@ -261,11 +161,6 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_shift_norm(int mode, int64_t n
   }
 }
 
-static int taylor_grid(int64_t n, int rows_per_block) {
-  int64_t g = (n + rows_per_block - 1) / rows_per_block;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(g, MAX_GRID));
-}
-
 }  // namespace dev
 
 // ------------------------------------------------------------------------------------------
@@ -308,6 +203,18 @@ static inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
 
 size_t taylor_head_bytes() { return sizeof(dev::TaylorState) + sizeof(double) * 2 * dev::MAX_GRID; }
 
+// (m*, s) and tol for tc.alpha, and the max_matvecs refusal
+void taylor_choose(const Op &op, int precision, int64_t max_matvecs, TaylorCall &tc) {
+  const int table = (precision == 1 || dtype_is_32bit(op.dtype)) ? 1 : 0;      // precision 0: the working precision of the operator's real type
+  taylor_params(table, tc.alpha, &tc.m, &tc.s);
+  const int m = tc.m;
+  const int64_t ns = tc.s;
+  if (max_matvecs > 0 && (unsigned __int128)ns * (unsigned)m > (unsigned __int128)max_matvecs)
+    fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: alpha = " + std::to_string(tc.alpha) + " needs m* = " + std::to_string(m) + " terms in each of s = " +
+                                     std::to_string(ns) + " stages, more than max_matvecs = " + std::to_string(max_matvecs));
+  tc.tol = table == 1 ? 0x1p-24 : 0x1p-53;
+}
+
 // What depends on A and t alone: mu, alpha (two launches and the one blocking read of a stored operator) and (m*, s).  `head`:
 // taylor_head_bytes() of device memory, zeroed here; its state block is ready for the first closing launch of a call afterwards.
 template <class T>
@@ -344,14 +251,7 @@ static void taylor_shift_plan_T(Ctx *c, Op &op, std::complex<double> t, int prec
   tc.mu_im = mu.imag();
   tc.alpha = std::abs(t) * anorm;
   if (std::abs(t) == 0.0 || anorm == 0.0) tc.alpha = 0.0;      // (0 * Inf: t = 0 returns b whatever A holds)
-  const int table = (precision == 1 || dtype_is_32bit(op.dtype)) ? 1 : 0;      // precision 0: the working precision of the operator's real type
-  taylor_params(table, tc.alpha, &tc.m, &tc.s);
-  const int m = tc.m;
-  const int64_t ns = tc.s;
-  if (max_matvecs > 0 && (unsigned __int128)ns * (unsigned)m > (unsigned __int128)max_matvecs)
-    fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: alpha = " + std::to_string(tc.alpha) + " needs m* = " + std::to_string(m) + " terms in each of s = " +
-                                     std::to_string(ns) + " stages, more than max_matvecs = " + std::to_string(max_matvecs));
-  tc.tol = table == 1 ? 0x1p-24 : 0x1p-53;
+  taylor_choose(op, precision, max_matvecs, tc);
 }
 
 // Every launch of one vector's series behind a plan: F = v = b, then s stages.  `st` is a zeroed state block (or the one the plan
@@ -386,7 +286,7 @@ static void taylor_run_T(Ctx *c, Op &op, std::complex<double> t, const void *b_d
   auto close = [&](const T *src, T *v, int sc, int64_t stage) {
     ProfScope ps(c, EXPV_MI_K_LINCOMB);
     hipLaunchKernelGGL(dev::k_taylor_close<T>, dim3(g_elem), dim3(dev::BLOCK), 0, s, src, F, v, n, taylor_scalar<T>(eta), sc,
-                       (int)std::min<int64_t>(stage, 2147483646), (int)(stage + 1 < ns), st);
+                       (int)std::min<int64_t>(stage, 2147483646), (int)(stage + 1 < ns), 0.0, st);
   };
   int p = 0;
   close(reinterpret_cast<const T *>(b_dev), V[0], 0, -1);
@@ -411,12 +311,15 @@ static void taylor_run_T(Ctx *c, Op &op, std::complex<double> t, const void *b_d
   HIPCHECK(hipGetLastError());
 }
 
-void taylor_shift_plan(Ctx *c, Op &op, double t_re, double t_im, int precision, int64_t max_matvecs, double opnorm, void *head, TaylorCall &tc) {
+void taylor_check(const Op &op, double t_im, int precision, double opnorm) {
   (void)taylor_table(precision);
   if (t_im != 0.0 && !dtype_is_complex(op.dtype))
     fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: a complex t needs a complex operator (a real operator with a complex result is not computed)");
   if (op.kind == OP_CALLBACK && !(opnorm > 0.0 && std::isfinite(opnorm)))
     fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: a matrix-free operator needs opnorm > 0, a bound on opnorm(A, Inf)");
+}
+void taylor_shift_plan(Ctx *c, Op &op, double t_re, double t_im, int precision, int64_t max_matvecs, double opnorm, void *head, TaylorCall &tc) {
+  taylor_check(op, t_im, precision, opnorm);
   dispatch_dtype(op.dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     taylor_shift_plan_T<T>(c, op, std::complex<double>(t_re, t_im), precision, max_matvecs, opnorm, head, tc);

@@ -473,17 +473,7 @@ void run_columns(Ctx *c, Op &op, double t_re, double t_im, BlockView Bv, BlockVi
   char *X = base + sbytes + 2 * vbytes;
   HIPCHECK(hipMemsetAsync(base, 0, sbytes, s));
   const int32_t *perm = op.perm ? op.perm->p.as<int32_t>() : nullptr, *pinv = op.perm ? op.perm->pinv.as<int32_t>() : nullptr;
-  auto copy = [&](BlockView from, BlockView to, const int32_t *idx) {
-    ProfScope ps(c, EXPV_MI_K_LINCOMB);
-    dispatch_dtype(op.dtype, [&](auto tag) {
-      using T = typename decltype(tag)::type;
-      for (int k0 = 0; k0 < ncols; k0 += 65535) {      // (gridDim.y <= 65535)
-        const dim3 g((unsigned)grid_of(n, dev::BLOCK), (unsigned)std::min(ncols - k0, 65535));
-        hipLaunchKernelGGL(dev::k_taylor_block_copy<T>, g, dim3(dev::BLOCK), 0, s, reinterpret_cast<const T *>(from.p) + (int64_t)k0 * from.cs, from.rs,
-                           from.cs, reinterpret_cast<T *>(to.p) + (int64_t)k0 * to.cs, to.rs, to.cs, idx, n);
-      }
-    });
-  };
+  auto copy = [&](BlockView from, BlockView to, const int32_t *idx) { taylor_block_copy(c, op, from.p, from.rs, from.cs, to.p, to.rs, to.cs, idx, ncols); };
   const BlockView Xv{X, 1, ldx};
   copy(Bv, Xv, perm);
   for (int k = 0; k < ncols; ++k) {
@@ -505,6 +495,19 @@ void run_columns(Ctx *c, Op &op, double t_re, double t_im, BlockView Bv, BlockVi
 }
 
 }  // namespace
+
+void taylor_block_copy(Ctx *c, Op &op, const void *src, int64_t srs, int64_t scs, void *dst, int64_t drs, int64_t dcs, const int32_t *idx, int ncols) {
+  ProfScope ps(c, EXPV_MI_K_LINCOMB);
+  const int64_t n = op.n;
+  dispatch_dtype(op.dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    for (int k0 = 0; k0 < ncols; k0 += 65535) {      // (gridDim.y <= 65535)
+      const dim3 g((unsigned)grid_of(n, dev::BLOCK), (unsigned)std::min(ncols - k0, 65535));
+      hipLaunchKernelGGL(dev::k_taylor_block_copy<T>, g, dim3(dev::BLOCK), 0, c->stream, reinterpret_cast<const T *>(src) + (int64_t)k0 * scs, srs, scs,
+                         reinterpret_cast<T *>(dst) + (int64_t)k0 * dcs, drs, dcs, idx, n);
+    }
+  });
+}
 
 void taylor_block_run(Ctx *c, Op &op, double t_re, double t_im, const void *B, int64_t ldb, int ncols, int b_layout, int b_loc, void *W,
                       int64_t ldw, int w_layout, int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[8],

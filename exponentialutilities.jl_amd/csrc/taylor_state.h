@@ -1,6 +1,8 @@
 // taylor_state.h -- the device-resident stage state of the truncated-Taylor exp(tA)b and the helpers its kernels share
-// (expv_taylor.hip: one vector; expv_taylor_block.hip: a block of columns).  gfx950 only.
+// (expv_taylor.hip: one vector; expv_taylor_block.hip: a block of columns; phiv_taylor.hip: the series on the augmented matrix, which
+// also launches the arrival / stopping-test / closing code below).  gfx950 only.
 #pragma once
+#include <algorithm>
 #include <complex>
 
 #include "kernel_common.h"
@@ -22,7 +24,7 @@ struct TaylorState {
   unsigned long long nf_stage;        // 0, or 1 + the stage (from 0) whose F was not finite
   unsigned long long mu_re, mu_im;    // tr(A) / n
   unsigned long long rowmax;          // max_i ( |a_ii - mu| + sum_{j != i} |a_ij| )
-  unsigned long long spare[2];
+  unsigned long long umax, wmax;      // phiv_taylor.hip: max |u_k[i]| and max_i sum_k |u_k[i]| over the columns k >= 1 of B
 };
 static_assert(sizeof(TaylorState) == 128, "TaylorState layout");
 
@@ -62,6 +64,116 @@ __device__ __forceinline__ double abs_T(cplx32 v) { return hypot((double)v.re, (
 __device__ __forceinline__ void note_abs(double a, double &m, unsigned &nan, unsigned bit) {
   if (a != a) nan |= bit;
   else m = fmax(m, a);
+}
+
+// ---- one launch of the series: arrival, the stopping test, the closing kernel (expv_taylor.hip, phiv_taylor.hip) ----
+
+// Every thread of every workgroup of a launch: this workgroup's maxima into the state, then one ticket.  True in the workgroup that
+// arrives last, whose lane 0 then owns the state (everything the others added was performed before their tickets).
+__device__ __forceinline__ bool taylor_arrive(TaylorState *st, double mv, double mf, unsigned nan) {
+  __shared__ double mv_s[BLOCK / 64], mf_s[BLOCK / 64];
+  __shared__ unsigned nan_s[BLOCK / 64];
+  __shared__ int last_s;
+  mv = wave_max(mv);
+  mf = wave_max(mf);
+  nan = (__any((int)(nan & 1u)) ? 1u : 0u) | (__any((int)(nan & 2u)) ? 2u : 0u) | (__any((int)(nan & 4u)) ? 4u : 0u);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { mv_s[wave] = mv; mf_s[wave] = mf; nan_s[wave] = nan; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < BLOCK / 64; ++w) { mv = fmax(mv, mv_s[w]); mf = fmax(mf, mf_s[w]); nan |= nan_s[w]; }
+    if (mv > 0.0) atomicMax(&st->maxv, (unsigned long long)__double_as_longlong(mv));
+    if (mf > 0.0) atomicMax(&st->maxf, (unsigned long long)__double_as_longlong(mf));
+    if (nan) atomicOr(&st->nanflags, (unsigned long long)nan);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned long long t = __hip_atomic_fetch_add(&st->ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last_s = (t == (unsigned long long)gridDim.x - 1ull);
+  }
+  __syncthreads();
+  return last_s != 0;
+}
+__device__ __forceinline__ void taylor_rearm(TaylorState *st) {
+  ts_store(&st->maxv, 0ull);
+  ts_store(&st->maxf, 0ull);
+  ts_store(&st->nanflags, 0ull);
+  ts_store(&st->ticket, 0ull);
+}
+// lane 0 of the last workgroup of a term launch: the test of the reference's loop (:153-155).  tail: a floor under |v|_inf (the part
+// of the term that lives outside the n rows, phiv_taylor.hip; 0 for exp(tA)b, where max(x, 0) = x for the non-negative maximum)
+__device__ __forceinline__ void taylor_term_test(TaylorState *st, double tol, int j, int m, double tail) {
+  const unsigned long long nan = ts_load(&st->nanflags);
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  const double c2 = (nan & 1ull) ? qnan : fmax(ts_loadf(&st->maxv), tail);
+  const double fn = (nan & 2ull) ? qnan : ts_loadf(&st->maxf);
+  const double c1 = ts_loadf(&st->c1);
+  ts_store(&st->apps, ts_load(&st->apps) + 1ull);
+  if (c1 + c2 <= tol * fn) {
+    ts_store(&st->stopped, 1ull);
+    if (j < m) ts_store(&st->early, ts_load(&st->early) + 1ull);
+  } else {
+    ts_storef(&st->c1, c2);
+  }
+  taylor_rearm(st);
+}
+__device__ __forceinline__ bool taylor_skip(const TaylorState *st) {
+  return (ts_load(&st->stopped) | ts_load(&st->ended)) != 0ull;
+}
+
+template <class T>
+struct TaylorTermArgs {
+  SellView<T> A;                                  // SELL slots (ndiag == 0) ...
+  const T *dia_val; int64_t dia_ld; int ndiag; const int32_t *dia_off;      // ... or the general diagonal form
+  const T *x;                                     // v of the previous term
+  T *y;                                           // fused: out.  update: in (A x as mul! left it) and out
+  T *F;
+  int64_t n;
+  T c, mu;                                        // (t / s) / j and tr(A) / n
+  double tol;
+  int j, m;
+  TaylorState *st;
+};
+
+// Closes a stage (:157-159): F = eta src (scale == 0: F = src as it is), v = F, c1 = |F|_inf, the finite test, and the state of the
+// next stage.  The first launch of a call is this kernel with src = b, scale = 0 and stage = -1 (no finite test: the reference
+// looks at F only after a stage).  tail: the floor under c1 of the stage that follows (taylor_term_test; 0 for exp(tA)b).
+template <class T>
+__global__ __launch_bounds__(BLOCK) void k_taylor_close(const T *src, T *F, T *v, int64_t n, T eta, int scale, int stage, int more,
+                                                        double tail, TaylorState *st) {
+  if (ts_load(&st->ended) != 0ull) return;
+  constexpr int N = Pack<T>::N;
+  const bool als = is_al16(src), alf = is_al16(F), alv = is_al16(v);
+  double mf = 0.0;
+  unsigned nan = 0u;
+  for (int64_t i = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * N; i < n; i += (int64_t)gridDim.x * BLOCK * N) {
+    Pack<T> f = ld_pack_user(src, i, n, als);
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      if (scale) f.v[k] = ST<T>::mul(eta, f.v[k]);
+      if (i + k < n) note_abs(abs_T(f.v[k]), mf, nan, 2u);
+    }
+    if (scale || src != F) st_pack_user(F, i, n, alf, f);
+    st_pack_user(v, i, n, alv, f);
+  }
+  if (taylor_arrive(st, 0.0, mf, nan) && threadIdx.x == 0) {
+    const double fn = (ts_load(&st->nanflags) & 2ull) ? __longlong_as_double(0x7ff8000000000000ll) : ts_loadf(&st->maxf);
+    ts_storef(&st->c1, fn != fn ? fn : fmax(fn, tail));
+    ts_storef(&st->fnorm, fn);
+    const bool finite = fn < __longlong_as_double(0x7ff0000000000000ll);
+    if (stage >= 0 && !finite) {
+      ts_store(&st->ended, 1ull);
+      ts_store(&st->nf_stage, (unsigned long long)stage + 1ull);
+    }
+    // a zero vector stays zero: the stage that follows applies nothing (b = 0 costs no operator application)
+    const bool zero = fn == 0.0 && tail == 0.0;
+    ts_store(&st->stopped, zero ? 1ull : 0ull);
+    if (zero && more) ts_store(&st->early, ts_load(&st->early) + 1ull);
+    taylor_rearm(st);
+  }
+}
+
+static int taylor_grid(int64_t n, int rows_per_block) {
+  int64_t g = (n + rows_per_block - 1) / rows_per_block;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(g, MAX_GRID));
 }
 
 }  // namespace dev

@@ -603,6 +603,38 @@ int expv_mi_expv_taylor_block(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, d
                               int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4], int64_t *col_info,
                               double *col_normF);
 
+/* w = phi_0(tA) u_0 + t phi_1(tA) u_1 + ... + t^p phi_p(tA) u_p for B = [u_0 ... u_p] (what phiv_timestep(t, A, B) returns) WITHOUT a
+ * Krylov basis: the series of expv_mi_expv_taylor on the augmented matrix of Al-Mohy & Higham (2011, Theorem 2.1 and section 5),
+ *       A~ = [A W; 0 J],  W = [u_p ... u_1],  J the p x p upward shift:  the first n rows of exp(t A~) [u_0; e_p] are w.
+ * A~ is never formed: the p tail components of every term do not depend on the data and are computed on the host in (complex)
+ * double, exactly as the recurrence defines them (the paper truncates them with the rest); the device keeps three work vectors of n
+ * elements and adds a combination of the columns of B to each term.
+ *   - B is n x ncols, ncols = p + 1, 1 <= ncols <= 9, in the operator's element type; layouts and locations as in
+ *     expv_mi_expv_taylor_block.  A column-major device block of an operator in its natural ordering is read where it lies; A ROW-MAJOR
+ *     DEVICE BLOCK IS TRANSPOSED ONCE into a column-major staging copy of n x ncols elements (so are a host block, copied, and the block
+ *     of a reordered operator, permuted).  w holds n elements and may be column 0 of B; overlap with any other column is
+ *     EXPV_MI_ARGUMENT_ERROR.  A reordered operator gets every column of B permuted on entry and w on exit.
+ *   - mu = tr(A) / (n + p);  U = max |u_k[i]| and Wmax = max_i sum_k |u_k[i]| over k >= 1;  nu = 2^-ceil(log2 Wmax) (1 for Wmax = 0): the
+ *     similarity diag(I, 1 / nu) changes nothing but the norm (the paper's guard against over-scaling);
+ *     alpha = |t| max( max_i (|a_ii - mu| + sum_{j != i} |a_ij| + nu sum_{k>=1} |u_k[i]|), 1 + |mu| ), the infinity norm of the scaled
+ *     A~ - mu I;  (m*, s) as expv_mi_host_taylor_params gives them.  Matrix-free operators: mu = 0 and opnorm stands for the A part
+ *     of every row sum.  A non-finite entry among u_1 .. u_p makes alpha non-finite: EXPV_MI_ARGUMENT_ERROR.
+ *   - Stage `stage` (tau = stage t / s, h = t / s) starts from zeta_0[i] = tau^(p-i) / (p-i)!, i = 1 .. p; term j:
+ *       v_j = (h / j) (A - mu I) v_{j-1} + sum_{k=1..p} g_j[p+1-k] u_k,  g_j = (h / j) zeta_{j-1},  zeta_j = (h / j)(J - mu I) zeta_{j-1},  F += v_j;
+ *     the g, rounded to the element type, travel by value.  The stopping test is that of expv_mi_expv_taylor with the tail as a
+ *     floor: c2 = max(|v_j|_inf, |zeta_j|_inf U), c1 at stage start max(|F|_inf, |zeta_0|_inf U), against |F|_inf of the n rows --
+ *     without the floor a call with u_0 = 0 would stop before the forcing has entered.  A launch whose g are all zero does not read
+ *     B (mu = 0: every term j > p).  A stage closes with F *= exp(mu h), v = F.
+ *   - ncols = 1 IS expv_mi_expv_taylor, bit for bit (mu = tr(A) / n, its alpha, no add).
+ *   - precision, max_matvecs, opnorm, the refusal of a complex t on a real operator, non-finite data in A or u_0, n = 0 and
+ *     "complete on return" are those of expv_mi_expv_taylor, with its messages.  ncols outside 1 .. 9, an unknown layout or loc and a
+ *     leading dimension too small are EXPV_MI_ARGUMENT_ERROR "phiv_taylor: ...", found before any device work.  A refused call
+ *     leaves w untouched.
+ * info (may be NULL): as expv_mi_expv_taylor; [5] <= 3.  dinfo (may be NULL): [0] alpha, [1] Re mu, [2] Im mu, [3] |F|_inf when the
+ * last stage closed, [4] nu, [5] U, [6], [7] 0. */
+int expv_mi_phiv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *B, int64_t ldb, int ncols, int b_layout,
+                        int b_loc, void *w, int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[8]);
+
 /* ------------------------------------------------------------------ time stepping ---- */
 typedef void (*expv_mi_print_fn)(const char *line, void *user);
 typedef struct {

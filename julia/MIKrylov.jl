@@ -694,6 +694,19 @@ function expv_taylor!(W::MIMatrix{T}, t::Number, A::MIOperator{T}, B::MIMatrix{T
     W
 end
 expv_taylor(t::Number, A::MIOperator{T}, B::MIMatrix{T}; kw...) where {T} = expv_taylor!(similar(B, T, size(B)), t, A, B; kw...)
+# The result of phiv_timestep(t, A, B), B = [u_0 ... u_p] with p <= 8, by the same series on Al-Mohy & Higham's augmented matrix:
+# w = sum_k t^k phi_k(tA) B[:, k].  No Krylov basis, no host exponential, three work vectors of length n; w may be B[:, 1].
+function phiv_taylor!(w::MIVector{T}, t::Number, A::MIOperator{T}, B::MIMatrix{T}; precision::Integer = 0, max_matvecs::Integer = 0,
+                      opnorm = nothing) where {T}
+    length(w) == size(B, 1) == size(A, 1) || throw(DimensionMismatch("length(w), size(B, 1) and size(A, 1) must agree"))
+    check(ccall((:expv_mi_phiv_taylor, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Cvoid}, Cint, Cint, Int64, Cdouble,
+                 Ptr{Int64}, Ptr{Cdouble}),
+                ctx().h, A.h, real(t), imag(t), B.ptr, ld(B), ncols(B), 0, DEVICE, w.ptr, DEVICE, precision, max_matvecs,
+                opnorm === nothing ? 0.0 : Float64(opnorm), C_NULL, C_NULL), ctx().h)
+    w
+end
+phiv_taylor(t::Number, A::MIOperator{T}, B::MIMatrix{T}; kw...) where {T} = phiv_taylor!(similar(B, T, (size(B, 1),)), t, A, B; kw...)
 
 # ---- error-estimate mode (Hermitian only)                                          (src/krylov_phiv_error_estimate.jl) ----
 struct MISubspaceCache end                                                     # stands in for StegrCache: the library owns the scratch
