@@ -132,6 +132,8 @@ PROTOTYPES = {
     "expv_mi_expv_taylor": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, _i64, _d, _pi64, _pd]),
     "expv_mi_expv_taylor_block": (_i, [_vp, _vp, _d, _d, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i, _i, _i64, _d, _pi64, _pd, _pi64, _pd]),
     "expv_mi_phiv_taylor": (_i, [_vp, _vp, _d, _d, _vp, _i64, _i, _i, _i, _vp, _i, _i, _i64, _d, _pi64, _pd]),
+    "expv_mi_expv_taylor_grid": (_i, [_vp, _vp, _d, _d, _pd, _i, _vp, _i, _vp, _i64, _i, _i, _i, _i64, _d, _pi64, _pd, _pi64]),
+    "expv_mi_host_taylor_grid_plan": (_i, [_i64, _pd, _i, _pi64, _pd, _pi]),
     "expv_mi_host_taylor_theta": (_i, [_i, _i, _pd]),
     "expv_mi_host_taylor_params": (_i, [_i, _d, _pi, _pi64]),
     "expv_mi_timestep_opts_default": (None, [C.POINTER(TimestepOpts)]),

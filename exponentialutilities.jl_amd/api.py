@@ -32,7 +32,7 @@ __all__ = [
     "phiv_timestep_", "kiops", "timestep_caches", "expv_batch", "expv_batch_multi", "RcclComm", "rccl_available", "rccl_unique_id", "ExpvMIError", "DimensionMismatch", "host_expm",
     "exponential", "exponential_", "mul_", "phi", "phi_", "balance_", "host_gebal",
     "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_dia_pattern", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
-    "expv_taylor", "expv_taylor_", "expv_taylor_block", "expv_taylor_block_", "phiv_taylor", "phiv_taylor_", "host_taylor_theta", "host_taylor_params",
+    "expv_taylor", "expv_taylor_", "expv_taylor_block", "expv_taylor_block_", "expv_taylor_grid", "expv_taylor_grid_", "host_taylor_grid_plan", "phiv_taylor", "phiv_taylor_", "host_taylor_theta", "host_taylor_params",
 ]
 
 ExpvMIError = L.ExpvMIError
@@ -1628,6 +1628,87 @@ def expv_taylor_block(t, A, B, *, precision=None, max_matvecs=0, opnorm=None, re
         W = np.empty(shape, dtype=T, order="F" if (Bn.flags.f_contiguous and not Bn.flags.c_contiguous) or
                      (not Bn.flags.c_contiguous and Bn.strides[0] == Bn.itemsize) else "C")
     return expv_taylor_block_(W, t, op, B, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
+
+
+_TAYLOR_GRID_INFO = _TAYLOR_INFO + ("accumulate_launches", "qmax")
+
+
+def _grid_multipliers(ts, t):
+    """(r, t'): the multipliers r_k = |ts_k| as a float64 array of its own and ``t`` with the common sign of ``ts`` folded in"""
+    r = np.array(_host_view(ts.detach().cpu() if _is_torch(ts) else ts), dtype=np.float64).ravel()
+    if np.any(r > 0) and np.any(r < 0):
+        raise L.ExpvMIError(2, "expv_taylor_grid: ts must be all >= 0 or all <= 0 (the sign is folded into t)")
+    if np.any(r < 0):
+        r, t = -r, -t
+    return np.ascontiguousarray(r), t
+
+
+def expv_taylor_grid_(W, ts, A, b, *, t=1.0, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """W[:, k] <- exp(ts[k] t A) b for a vector of real times in ONE sweep of the truncated Taylor series of expv_taylor_
+    (expv_mi_expv_taylor_grid): with R = max |ts|, the call is expv_taylor_'s for R t -- its mu, alpha, m*, s, its F and v,
+    operation for operation -- and every other output is read off the terms of the stage it falls into, at no extra pass over
+    the operator.  Columns with |ts[k]| = R are bit for bit ``expv_taylor(R t, A, b)``; ts[k] = 0 gives b.  ``ts``: real, all
+    >= 0 or all <= 0 (the sign goes into ``t``; mixed signs are an ArgumentError), any order, duplicates allowed, not modified.
+    ``W``: an (n, len(ts)) block as expv_taylor_block_ takes it; it may not overlap ``b``.  ``precision``, ``max_matvecs``
+    (against m* s), ``opnorm`` and a complex ``t`` as in expv_taylor_.  ``return_info``: also return the dictionary kept in
+    ``expv_taylor_grid.last_info``: the keys of expv_taylor_ (applications = term launches that did work, shared by all outputs),
+    accumulate_launches, qmax (the most interior outputs of one stage) and the per-output lists stage (-1 for ts[k] = 0), terms,
+    kind (0 = b, 1 = interior, 2 = stage end)."""
+    r, t = _grid_multipliers(ts, t)
+    tr, ti, _ = _t_parts(t)
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(b))
+    opT = _as_operator(op, T)
+    ba, wa = _Arg(_host_view(b), T), _BlockArg(W, T, writable=True)
+    n, q = opT.shape[0], int(r.size)
+    if int(np.prod(ba.shape)) != n:
+        raise DimensionMismatch(f"length(b) [{int(np.prod(ba.shape))}] == size(A,1) [{n}] doesn't hold")
+    if wa.shape != (n, q):
+        raise DimensionMismatch(f"size(W) [{wa.shape}] == (size(A,1), length(ts)) [{(n, q)}] doesn't hold")
+    info, dinfo = (C.c_int64 * 10)(), (C.c_double * 4)()
+    cinfo = (C.c_int64 * max(3 * q, 1))()
+    _check(L.load().expv_mi_expv_taylor_grid(opT.ctx._h, opT._h, tr, ti, r.ctypes.data_as(C.POINTER(C.c_double)), q, ba.ptr, ba.loc, wa.ptr,
+                                             wa.ld, wa.layout, wa.loc, int(precision or 0), int(max_matvecs),
+                                             0.0 if opnorm is None else float(opnorm), info, dinfo, cinfo), opT.ctx._h)
+    wa.finish()
+    d = dict(zip(_TAYLOR_GRID_INFO, (int(v) for v in info)))
+    d.update(alpha=float(dinfo[0]), mu=complex(dinfo[1], dinfo[2]) if T.kind == "c" else float(dinfo[1]), normF=float(dinfo[3]),
+             stage=[int(cinfo[3 * k]) for k in range(q)], terms=[int(cinfo[3 * k + 1]) for k in range(q)],
+             kind=[int(cinfo[3 * k + 2]) for k in range(q)])
+    expv_taylor_grid.last_info = d
+    return (W, d) if return_info else W
+
+
+def expv_taylor_grid(ts, A, b, *, t=1.0, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """exp(ts[k] t A) b for a vector of real times (see expv_taylor_grid_): an (n, len(ts)) result that lives where ``b`` does --
+    Fortran order for numpy, a contiguous (n, q) tensor for torch -- in the element type the device worked in.  A scalar ``ts``
+    returns the vector ``expv_taylor(ts * t, A, b)``, bit for bit."""
+    if np.ndim(_host_view(ts) if not (_is_torch(ts) and ts.is_cuda) else ts.cpu()) == 0:
+        return expv_taylor(float(ts) * t, A, b, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
+    _grid_multipliers(ts, t)      # (mixed signs: refused before anything is created)
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(b))
+    shape = (int(b.shape[0]), int(np.size(_host_view(ts) if not _is_torch(ts) else ts.cpu())))
+    if isinstance(b, DeviceArray):
+        W = DeviceArray(shape, T, b.ctx)
+    elif _is_torch(b):
+        import torch
+        W = torch.empty(shape, dtype=_torch_dtype(T), device=b.device)
+    else:
+        W = np.empty(shape, dtype=T, order="F")
+    return expv_taylor_grid_(W, ts, op, b, t=t, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
+
+
+def host_taylor_grid_plan(s, r):
+    """The classification of expv_taylor_grid's outputs for ``s`` stages and multipliers ``r`` >= 0 (expv_mi_host_taylor_grid_plan;
+    host only): (stage, rho, kind) as int64 / float64 / int32 arrays -- x = s (r / max r), stage = max(ceil(x) - 1, 0), rho = x - stage;
+    kind 0: r = 0 (stage -1, rho 0), 2: rho = 1 (a stage end), 1: interior."""
+    r = np.ascontiguousarray(np.asarray(r, dtype=np.float64).ravel())
+    q = int(r.size)
+    stage, rho, kind = np.zeros(max(q, 1), dtype=np.int64), np.zeros(max(q, 1), dtype=np.float64), np.zeros(max(q, 1), dtype=np.int32)
+    _check(L.load().expv_mi_host_taylor_grid_plan(int(s), r.ctypes.data_as(C.POINTER(C.c_double)), q, stage.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  rho.ctypes.data_as(C.POINTER(C.c_double)), kind.ctypes.data_as(C.POINTER(C.c_int))))
+    return stage[:q], rho[:q], kind[:q]
 
 
 def phiv_taylor_(w, t, A, B, *, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):

@@ -2879,6 +2879,42 @@ int expv_mi_phiv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double 
     phiv_taylor_run(ctx, *op, t_re, t_im, B, ldb, ncols, b_layout, b_loc, w, w_loc, precision, max_matvecs, opnorm, info, dinfo);
   });
 }
+int expv_mi_expv_taylor_grid(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const double *r, int nt, const void *b, int b_loc,
+                             void *W, int64_t ldw, int w_layout, int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[10],
+                             double dinfo[4], int64_t *col_info) {
+  return guarded(ctx, [&] {
+    if (info) std::fill(info, info + 10, (int64_t)0);
+    if (dinfo) std::fill(dinfo, dinfo + 4, 0.0);
+    if (!ctx || !op) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_grid: null context / operator");
+    taylor_grid_plan(1, r, nt, nullptr, nullptr, nullptr);      // (nt and the multipliers)
+    if ((b_loc != EXPV_MI_HOST && b_loc != EXPV_MI_DEVICE) || (w_loc != EXPV_MI_HOST && w_loc != EXPV_MI_DEVICE))
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_grid: unknown loc");
+    if (w_layout != EXPV_MI_BLOCK_COL_MAJOR && w_layout != EXPV_MI_BLOCK_ROW_MAJOR)
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_grid: unknown layout (0 = column-major, 1 = row-major)");
+    const int64_t n = op->n;
+    if (n == 0 || nt == 0) return;
+    const bool colmajor = w_layout == EXPV_MI_BLOCK_COL_MAJOR;
+    if (ldw < (colmajor ? n : (int64_t)nt))
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_grid: leading dimension too small (ldw = " + std::to_string(ldw) + " for an " + std::to_string(n) + " x " +
+                                       std::to_string(nt) + " block)");
+    if (!b || !W) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_grid: null pointer");
+    const size_t esz = dtype_size(op->dtype);
+    if (b_loc == w_loc) {      // (the outputs are written while b is still being read)
+      const size_t wext = (size_t)(colmajor ? (nt - 1) * ldw + n : (n - 1) * ldw + nt) * esz;
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(b), w0 = reinterpret_cast<uintptr_t>(W);
+      if (b0 < w0 + wext && w0 < b0 + (size_t)n * esz) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_grid: W overlaps b");
+    }
+    taylor_check(*op, t_im, precision, opnorm);
+    for (int k = 0; col_info && k < 3 * nt; ++k) col_info[k] = 0;
+    ctx->use();
+    DevBuf tmp;
+    const void *bd = vector_in(ctx, *op, b, b_loc, n, esz, tmp);
+    taylor_grid_run(ctx, *op, t_re, t_im, r, nt, bd, W, ldw, w_layout, w_loc, precision, max_matvecs, opnorm, info, dinfo, col_info);
+  });
+}
+int expv_mi_host_taylor_grid_plan(int64_t s, const double *r, int nt, int64_t *stage, double *rho, int *kind) {
+  return guarded(nullptr, [&] { taylor_grid_plan(s, r, nt, stage, rho, kind); });
+}
 int expv_mi_host_taylor_theta(int precision, int m, double *theta) {
   return guarded(nullptr, [&] {
     if (!theta) fail(EXPV_MI_ARGUMENT_ERROR, "host_taylor_theta: null output");

@@ -604,6 +604,18 @@ void taylor_block_run(Ctx *ctx, Op &op, double t_re, double t_im, const void *B,
 void taylor_block_copy(Ctx *ctx, Op &op, const void *src, int64_t srs, int64_t scs, void *dst, int64_t drs, int64_t dcs, const int32_t *idx,
                        int ncols);
 
+// a host block <-> its compact device copy of the same layout (the elements between the columns / rows of a padded ld stay out of it)
+void taylor_block_copy_host(hipStream_t s, void *dst, int64_t ld_dst, const void *src, int64_t ld_src, int layout, int64_t n, int ncols, size_t esz,
+                            hipMemcpyKind kind);
+
+// ---- expv_taylor_grid.hip -------------------------------------------------------------------
+// exp(r_k t A) b for nt multipliers in one sweep of the series (include/expv_mi.h: expv_mi_expv_taylor_grid); b_dev is on the device in
+// the operator's stored ordering, the other arguments have been checked by the caller.  taylor_grid_plan: the classification of the
+// outputs for s stages (host only; it refuses a negative nt and a negative, NaN or infinite multiplier).
+void taylor_grid_run(Ctx *ctx, Op &op, double t_re, double t_im, const double *r, int nt, const void *b_dev, void *W, int64_t ldw, int w_layout,
+                     int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[10], double dinfo[4], int64_t *col_info);
+void taylor_grid_plan(int64_t s, const double *r, int nt, int64_t *stage, double *rho, int *kind);
+
 // ---- phiv_taylor.hip ------------------------------------------------------------------------
 // w = sum_k t^k phi_k(tA) u_k for B = [u_0 ... u_p] by the same series (include/expv_mi.h: expv_mi_phiv_taylor); the arguments have
 // been checked by the caller.

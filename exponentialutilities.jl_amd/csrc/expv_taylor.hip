@@ -281,7 +281,7 @@ static void taylor_run_T(Ctx *c, Op &op, std::complex<double> t, const void *b_d
   constexpr int SH = 64 * dev::Pack<T>::N;
   const int g_fused = dev::taylor_grid((n + SH - 1) / SH, dev::BLOCK / 64);
   const int g_elem = dev::taylor_grid(n, dev::BLOCK * dev::Pack<T>::N);
-  const std::complex<double> eta = std::exp(mu * t / (double)ns);
+  const std::complex<double> eta = taylor_stage_factor(mu, t, ns);
   const bool scale = !(eta.real() == 1.0 && eta.imag() == 0.0);
   auto close = [&](const T *src, T *v, int sc, int64_t stage) {
     ProfScope ps(c, EXPV_MI_K_LINCOMB);

@@ -135,35 +135,7 @@ __device__ __forceinline__ unsigned block_mask(const unsigned long long *a, cons
 }
 __device__ __forceinline__ double block_qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
-// The roundings of `mul(c, a)` and `F + mul(c, a)` as k_taylor_term_fused, k_taylor_term_update and k_taylor_close are compiled.
-// ST<T>::mul and ST<T>::add are written as products and sums, and the compiler contracts them where it meets them:
-//   real types      y = c a rounded, F + c a ONE fused multiply-add;
-//   complex types   re = fma(c.re, a.re, -(c.im a.im)) in both; im = fma(c.re, a.im, c.im a.re) in ComplexF64 but
-//                   fma(c.im, a.re, c.re a.im) in ComplexF32 (a packed instruction pairs the operands the other way); F + y plain sums.
-// Which product it fuses depends on the code around (the masking here hides the real product from the sum, and the complex close
-// came out the other way round), so this file spells the single kernels' operations out as explicit fused multiply-adds: a product
-// that only feeds an fma, and a sum of an fma, leave nothing to contract.  Nothing pins the compiler's choice THERE:
-// tests/test_gpu_expv_taylor_block.py holds the two to the same bits, for every element type.
-__device__ __forceinline__ double mul_as_single(double c, double a) { return c * a; }
-__device__ __forceinline__ float mul_as_single(float c, float a) { return c * a; }
-__device__ __forceinline__ cplx mul_as_single(cplx c, cplx a) {
-  const double pr = c.im * a.im, pi = c.im * a.re;
-  return make_cplx(fma(c.re, a.re, -pr), fma(c.re, a.im, pi));
-}
-__device__ __forceinline__ cplx32 mul_as_single(cplx32 c, cplx32 a) {
-  const float pr = c.im * a.im, pi = c.re * a.im;
-  return make_cplx32(fmaf(c.re, a.re, -pr), fmaf(c.im, a.re, pi));
-}
-// F + c a, given y = mul_as_single(c, a)
-template <class T>
-__device__ __forceinline__ T term_sum(T f, T c, T a, T y) {
-  if constexpr (ST<T>::is_complex) {
-    return ST<T>::add(f, y);
-  } else {
-    ST<T>::fma_(f, c, a);
-    return f;
-  }
-}
+// (mul_as_single and term_sum, which hold the roundings of the single kernels: taylor_state.h, shared with expv_taylor_grid.hip)
 
 template <class T>
 struct BlockTermArgs {
@@ -404,7 +376,7 @@ void run_panels(Ctx *c, Op &op, std::complex<double> t, BlockView Bv, BlockView 
   }
   a.F = F; a.n = n; a.mu = taylor_scalar<T>(mu); a.tol = tc.tol; a.m = m;
   const int g_term = grid_of(nsl, dev::BLOCK / 64), g_rows = grid_of(rows, dev::BLOCK);
-  const std::complex<double> eta = std::exp(mu * t / (double)ns);
+  const std::complex<double> eta = taylor_stage_factor(mu, t, ns);
   const bool scale = !(eta.real() == 1.0 && eta.imag() == 0.0);
   const int32_t *perm = op.perm ? op.perm->p.as<int32_t>() : nullptr, *pinv = op.perm ? op.perm->pinv.as<int32_t>() : nullptr;
 
@@ -495,6 +467,11 @@ void run_columns(Ctx *c, Op &op, double t_re, double t_im, BlockView Bv, BlockVi
 }
 
 }  // namespace
+
+void taylor_block_copy_host(hipStream_t s, void *dst, int64_t ld_dst, const void *src, int64_t ld_src, int layout, int64_t n, int ncols, size_t esz,
+                            hipMemcpyKind kind) {
+  copy_block(s, dst, ld_dst, src, ld_src, layout, n, ncols, esz, kind);
+}
 
 void taylor_block_copy(Ctx *c, Op &op, const void *src, int64_t srs, int64_t scs, void *dst, int64_t drs, int64_t dcs, const int32_t *idx, int ncols) {
   ProfScope ps(c, EXPV_MI_K_LINCOMB);

@@ -3,6 +3,7 @@
 // also launches the arrival / stopping-test / closing code below).  gfx950 only.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <complex>
 
 #include "kernel_common.h"
@@ -171,12 +172,53 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_close(const T *src, T *F, T *v
   }
 }
 
+// The roundings of `mul(c, a)` and `F + mul(c, a)` as k_taylor_term_fused, k_taylor_term_update and k_taylor_close are compiled.
+// ST<T>::mul and ST<T>::add are written as products and sums, and the compiler contracts them where it meets them:
+//   real types      y = c a rounded, F + c a ONE fused multiply-add;
+//   complex types   re = fma(c.re, a.re, -(c.im a.im)) in both; im = fma(c.re, a.im, c.im a.re) in ComplexF64 but
+//                   fma(c.im, a.re, c.re a.im) in ComplexF32 (a packed instruction pairs the operands the other way); F + y plain sums.
+// Which product it fuses depends on the code around (the masking here hides the real product from the sum, and the complex close
+// came out the other way round), so the block and grid kernels spell the single kernels' operations out as explicit fused multiply-adds: a product
+// that only feeds an fma, and a sum of an fma, leave nothing to contract.  Nothing pins the compiler's choice THERE:
+// tests/test_gpu_expv_taylor_block.py and tests/test_gpu_expv_taylor_grid.py hold them to the same bits, for every element type.
+__device__ __forceinline__ double mul_as_single(double c, double a) { return c * a; }
+__device__ __forceinline__ float mul_as_single(float c, float a) { return c * a; }
+__device__ __forceinline__ cplx mul_as_single(cplx c, cplx a) {
+  const double pr = c.im * a.im, pi = c.im * a.re;
+  return make_cplx(fma(c.re, a.re, -pr), fma(c.re, a.im, pi));
+}
+__device__ __forceinline__ cplx32 mul_as_single(cplx32 c, cplx32 a) {
+  const float pr = c.im * a.im, pi = c.re * a.im;
+  return make_cplx32(fmaf(c.re, a.re, -pr), fmaf(c.im, a.re, pi));
+}
+// F + c a, given y = mul_as_single(c, a)
+template <class T>
+__device__ __forceinline__ T term_sum(T f, T c, T a, T y) {
+  if constexpr (ST<T>::is_complex) {
+    return ST<T>::add(f, y);
+  } else {
+    ST<T>::fma_(f, c, a);
+    return f;
+  }
+}
+
 static int taylor_grid(int64_t n, int rows_per_block) {
   int64_t g = (n + rows_per_block - 1) / rows_per_block;
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, MAX_GRID));
 }
 
 }  // namespace dev
+
+// The stage factor exp(mu t / s) in double.  The complex product is spelled out: written as mu * t the host compiler fuses one
+// product of each component into a multiply-add and picks WHICH ONE from the code around, so that two callers disagree in the last
+// bit when mu and t are both complex -- and with them every bit-for-bit promise between the single, block and grid calls.  With
+// the product written out nothing is left to choose.  (For a real mu or a real t every form rounds alike; for a complex mu with a
+// complex t the factor of expv_taylor and expv_taylor_block may differ in its last bit from what they computed before this helper.)
+static inline std::complex<double> taylor_stage_factor(std::complex<double> mu, std::complex<double> t, int64_t ns) {
+  const double pr = mu.imag() * t.imag(), pi = mu.imag() * t.real();
+  const double re = std::fma(mu.real(), t.real(), -pr), im = std::fma(mu.real(), t.imag(), pi);
+  return std::exp(std::complex<double>(re / (double)ns, im / (double)ns));
+}
 
 // a host scalar rounded to the element type the kernels take it in
 template <class T> static inline T taylor_scalar(std::complex<double> z) {

@@ -603,6 +603,46 @@ int expv_mi_expv_taylor_block(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, d
                               int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4], int64_t *col_info,
                               double *col_normF);
 
+/* W(:, k) = exp(r_k t A) b for nt real multipliers r_k >= 0 (any order, duplicates allowed) in ONE sweep of the series of
+ * expv_mi_expv_taylor: the time grid of the basis-free family (saveat, dense output, a propagator sampled along a ray).
+ *   - R = max r_k, T = R t;  mu, alpha = |T| opnorm(A - mu I, Inf) and (m*, s) are those of expv_mi_expv_taylor for T;  h = T / s.
+ *     Output k is classified in double, with exactly these expressions (expv_mi_host_taylor_grid_plan):
+ *         x_k = s (r_k / R),  i_k = max(ceil(x_k) - 1, 0),  rho_k = x_k - i_k
+ *     r_k = 0: the output is b, bit for bit (kind 0).  rho_k = 1: a copy of F after stage i_k has closed (kind 2).  Otherwise an
+ *     interior output of stage i_k (kind 1): within a stage the terms v_j = (hA)^j F / j! are all there, and
+ *     exp(rho h A) F = sum_j rho^j v_j, so no output costs a pass over the operator.
+ *   - F and v run exactly as in expv_mi_expv_taylor, operation for operation: EVERY OUTPUT WITH r_k = R IS BIT FOR BIT what
+ *     expv_mi_expv_taylor returns for (R t_re, R t_im).  An interior output starts as G_k = F with d_k0 = 1; at term j
+ *     d_kj = d_k,j-1 rho_k in double, rounded to the operator's real type and passed by value, and G_k += d_kj v_j (one fused
+ *     multiply-add per real component).  Its stopping test, on the device: c2 = d_kj |v_j|_inf, c1 starts as the stage's c1, stop
+ *     when c1 + c2 <= tol |G_k|_inf, else c1 = c2.  A stopped output is masked (written back unchanged, no maxima); so is F once
+ *     its own test has passed; v_j keeps being computed while F or any output of the stage is live, and a term launch returns at
+ *     once when all of them have stopped or the call has ended.  The output closes with G_k <- exp(mu rho_k h) G_k (skipped when
+ *     that factor is exactly 1).  The interior outputs of a stage live in panels of 8 interleaved columns (the remainder in the
+ *     smallest panel of 2, 4 or 8): the first panel is updated in the epilogue of the term kernel, each further one by an
+ *     accumulate-only launch per term that reads v_j once.  Workspace: the three vectors of the single call and
+ *     n x 8 ceil(q_max / 8) elements, q_max the most interior outputs of one stage.
+ *   - A non-finite F at the close of stage i ends the loop as in expv_mi_expv_taylor; every output of a later stage is the
+ *     non-finite F as it stands; the status is OK.  alpha = 0 or t = 0: output k is exp(mu r_k t) b (b bit for bit when the factor
+ *     is 1).  b = 0: zeros, no application.  nt = 0 or n = 0 does nothing.
+ *   - W is n x nt in the operator's element type, layout and leading dimension as in expv_mi_expv_taylor_block, and lives where
+ *     w_loc says; b lives where b_loc says; W may not overlap b.  A reordered operator answers in the caller's ordering.
+ *   - nt < 0, a negative, NaN or infinite r_k, an unknown layout or loc, ldw too small and W overlapping b are
+ *     EXPV_MI_ARGUMENT_ERROR "expv_taylor_grid: ...", found before any device work; precision, a complex t on a real operator, a
+ *     matrix-free operator without opnorm and max_matvecs (against m* s) are refused as by expv_mi_expv_taylor, with its messages.
+ *     A refused call leaves W untouched.  Complete on return.
+ * info (may be NULL): [0..7] as expv_mi_expv_taylor: [2] = term launches that did work (operator applications, shared by all
+ * outputs), [3] = stages whose F stopped before m*, [4] = term launches enqueued (m* s), [5] <= 2; [8] = accumulate-only launches
+ * enqueued, [9] = q_max.  dinfo (may be NULL): as expv_mi_expv_taylor.  col_info (NULL or 3 nt words), for output k: [3k] its stage
+ * (-1 for r_k = 0), [3k+1] the terms that entered it (stage end: the terms F took in that stage), [3k+2] its kind: 0 = b,
+ * 1 = interior, 2 = stage end. */
+int expv_mi_expv_taylor_grid(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const double *r, int nt, const void *b, int b_loc,
+                             void *W, int64_t ldw, int w_layout, int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[10],
+                             double dinfo[4], int64_t *col_info);
+/* Host only: the classification above for s stages: stage[k] = i_k (-1 for r_k = 0), rho[k] (0 for r_k = 0), kind[k]; each output
+ * pointer may be NULL.  nt < 0, s < 1 and a negative, NaN or infinite r_k are EXPV_MI_ARGUMENT_ERROR. */
+int expv_mi_host_taylor_grid_plan(int64_t s, const double *r, int nt, int64_t *stage, double *rho, int *kind);
+
 /* w = phi_0(tA) u_0 + t phi_1(tA) u_1 + ... + t^p phi_p(tA) u_p for B = [u_0 ... u_p] (what phiv_timestep(t, A, B) returns) WITHOUT a
  * Krylov basis: the series of expv_mi_expv_taylor on the augmented matrix of Al-Mohy & Higham (2011, Theorem 2.1 and section 5),
  *       A~ = [A W; 0 J],  W = [u_p ... u_1],  J the p x p upward shift:  the first n rows of exp(t A~) [u_0; e_p] are w.

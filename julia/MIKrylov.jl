@@ -694,6 +694,24 @@ function expv_taylor!(W::MIMatrix{T}, t::Number, A::MIOperator{T}, B::MIMatrix{T
     W
 end
 expv_taylor(t::Number, A::MIOperator{T}, B::MIMatrix{T}; kw...) where {T} = expv_taylor!(similar(B, T, size(B)), t, A, B; kw...)
+# A time grid: W[:, k] = exp(ts[k] t A) b in ONE sweep of the series -- the call is expv_taylor's for R t, R = max |ts|, and every other
+# output is read off the terms of the stage it falls into, at no extra pass over the operator.  ts: real, all >= 0 or all <= 0 (the
+# sign goes into t), any order, duplicates allowed; columns with |ts[k]| = R are bit for bit expv_taylor(R t, A, b); W may not overlap b.
+function expv_taylor!(W::MIMatrix{T}, ts::AbstractVector{<:Real}, A::MIOperator{T}, b::MIVector{T}; t::Number = 1.0, precision::Integer = 0,
+                      max_matvecs::Integer = 0, opnorm = nothing) where {T}
+    size(W) == (length(b), length(ts)) && length(b) == size(A, 1) || throw(DimensionMismatch("size(W) must be (length(b), length(ts)) and length(b) == size(A, 1)"))
+    any(>(0), ts) && any(<(0), ts) && throw(ArgumentError("expv_taylor: ts must be all >= 0 or all <= 0 (the sign is folded into t)"))
+    r = Float64[abs(x) for x in ts]
+    any(<(0), ts) && (t = -t)
+    check(ccall((:expv_mi_expv_taylor_grid, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint, Cint, Cint, Int64,
+                 Cdouble, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}),
+                ctx().h, A.h, real(t), imag(t), r, length(r), b.ptr, DEVICE, W.ptr, ld(W), 0, DEVICE, precision, max_matvecs,
+                opnorm === nothing ? 0.0 : Float64(opnorm), C_NULL, C_NULL, C_NULL), ctx().h)
+    W
+end
+expv_taylor(ts::AbstractVector{<:Real}, A::MIOperator{T}, b::MIVector{T}; kw...) where {T} =
+    expv_taylor!(similar(b, T, (length(b), length(ts))), ts, A, b; kw...)
 # The result of phiv_timestep(t, A, B), B = [u_0 ... u_p] with p <= 8, by the same series on Al-Mohy & Higham's augmented matrix:
 # w = sum_k t^k phi_k(tA) B[:, k].  No Krylov basis, no host exponential, three work vectors of length n; w may be B[:, 1].
 function phiv_taylor!(w::MIVector{T}, t::Number, A::MIOperator{T}, B::MIMatrix{T}; precision::Integer = 0, max_matvecs::Integer = 0,
