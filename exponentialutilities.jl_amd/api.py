@@ -600,8 +600,9 @@ class MIOperator:
     (expv_mi_op_create_bsr_loc) and the front ends take such a tensor as ``A`` too; a scipy ``bsr_matrix`` handed to the plain
     constructor or front ends keeps going through ``.tocsc()``.  Stored diagonals (a scipy ``dia_matrix``, or a 2-D tensor / array
     with one row per diagonal and the offsets) come in through ``MIOperator.from_dia`` (expv_mi_op_create_dia_loc); the plain
-    constructor treats a scipy ``dia_matrix`` as before.  Exposes ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian),
-    ``nnz`` and ``opnorm_inf``.
+    constructor treats a scipy ``dia_matrix`` as before.  ``A.adjoint()`` / ``A.transpose()`` (``A.H`` / ``A.T``) build the operator
+    of ``A'`` / ``transpose(A)`` on the device from what ``A`` stores (expv_mi_op_create_adjoint): ``expv(t, A.H, b)``.  Exposes
+    ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian), ``nnz`` and ``opnorm_inf``.
     """
 
     def __init__(self, A, ctx=None, dtype=None, ishermitian=None, matvec=None, shape=None, matvec_c=None, _coo=None, _bsr=None, _dia=None):
@@ -954,6 +955,9 @@ class MIOperator:
         fmt = getattr(self, "_sp_format", None)
         if fmt is None:
             raise ValueError("update_values: sparse operators only")
+        if getattr(self, "_adj_how", 0) and (_is_torch_sparse(A) or hasattr(A, "indptr")):
+            raise TypeError("update_values: an operator made by adjoint() / transpose() takes bare values in its own sorted-row order; "
+                            "to follow its parent use refresh(parent), for another element type parent.astype(dtype).adjoint()")
         if fmt == "coo":
             return self._update_coo(A)
         if fmt == "bsr":
@@ -1084,10 +1088,68 @@ class MIOperator:
             delattr(self, key)
         return self
 
+    def _adjoint(self, how):
+        lib = L.load()
+        h = C.c_void_p()
+        _check(lib.expv_mi_op_create_adjoint(self._h, how, C.byref(h)), self.ctx._h)
+        op = object.__new__(MIOperator)
+        op.ctx, op.src, op._cb, op._matvec, op._h = self.ctx, None, None, None, h
+        op._finalizer = weakref.finalize(op, lib.expv_mi_op_destroy, h)
+        op._adj_how = how
+        op.src_dtype = self.src_dtype
+        if getattr(self, "_sp_format", None) is not None:      # sparse: bare values refresh it in its own sorted-row order
+            op._sp_format, op._sp_sorted = "csr", True
+        op._read_info()
+        return op
+
+    def _read_info(self):
+        n_, nnz, herm, opn, dtc = C.c_int64(), C.c_int64(), C.c_int(), C.c_double(), C.c_int()
+        _check(L.load().expv_mi_op_info(self._h, C.byref(n_), C.byref(nnz), C.byref(herm), C.byref(opn), C.byref(dtc)))
+        self.shape = (int(n_.value), int(n_.value))
+        self.nnz = int(nnz.value)
+        self.ishermitian = bool(herm.value)
+        self.opnorm_inf = float(opn.value)
+        self.dtype = np.dtype({L.F64: np.float64, L.C64: np.complex128, L.F32: np.float32, L.C32: np.complex64}[dtc.value])
+
+    def adjoint(self):
+        """The operator of ``A' = conj(transpose(A))`` as a NEW, independent ``MIOperator`` on the same context
+        (expv_mi_op_create_adjoint): built on the device from what this operator stores, whatever it was created from -- sparse of
+        any birth, reordered or not, or dense (an owned packed copy); the values never visit the host.  ``expv(t, A.adjoint(), b)``
+        is the reference's ``expv(t, A', b)``: the adjoint-sensitivity call, the left-eigenvector call.  It does not follow later
+        changes of ``A`` (``refresh`` does that) and survives ``A``.  ``shape``, ``dtype``, ``nnz``, ``ishermitian`` and
+        ``opnorm_inf`` are filled as for any operator -- ``A.adjoint().opnorm_inf`` is the one-norm of ``A``.  ``src`` is ``None``:
+        ``astype`` is refused (``A.astype(dtype).adjoint()``), ``update_values`` takes bare values only, nnz of them in the
+        adjoint's own sorted-row order (the column-major order of ``A``).  A matrix-free operator has no adjoint (Unsupported).
+        ``A.H`` is an alias and, as in scipy, builds a new operator at every access: keep the result."""
+        return self._adjoint(L.OP_ADJOINT)
+
+    def transpose(self):
+        """The operator of ``transpose(A)``, no conjugation: see ``adjoint``, with which it shares everything else (for the real
+        element types also the bits).  ``A.T`` is an alias that builds a new operator at every access."""
+        return self._adjoint(L.OP_TRANSPOSE)
+
+    H = property(adjoint, doc="``adjoint()``: a new operator at every access (the scipy convention), not cached")
+    T = property(transpose, doc="``transpose()``: a new operator at every access (the scipy convention), not cached")
+
+    def refresh(self, parent):
+        """Of an operator made by ``adjoint()`` / ``transpose()``: take the CURRENT values of ``parent`` -- the operator it was
+        made from, or one of the same pattern -- on the device (expv_mi_op_adjoint_refresh) and re-evaluate ``ishermitian`` /
+        ``opnorm_inf``; bit-equal to ``parent.adjoint()`` made anew.  Another pattern with the same counts is the caller's error."""
+        if not getattr(self, "_adj_how", 0):
+            raise TypeError("refresh: only an operator made by adjoint() / transpose() refreshes from a parent")
+        if not isinstance(parent, MIOperator):
+            raise TypeError("refresh: the parent must be an MIOperator")
+        _check(L.load().expv_mi_op_adjoint_refresh(self._h, parent._h), self.ctx._h)
+        self._read_info()
+        return self
+
     def astype(self, dtype):
         dtype = _work_dtype(dtype)
         if dtype == self.dtype:
             return self
+        if getattr(self, "_adj_how", 0):
+            raise TypeError("an operator made by adjoint() / transpose() keeps no source to convert: use parent.astype(dtype).adjoint() "
+                            "(and refresh(parent.astype(dtype)) after the parent changes)")
         if getattr(self, "_sp_format", None) == "dia":      # rebuilt from the kept diagonals (on the device when they are there)
             key = "_as_" + dtype.name
             if not hasattr(self, key):

@@ -2126,6 +2126,36 @@ int expv_mi_op_ingest_info(expv_mi_op_t op, int64_t out[8]) {
   return EXPV_MI_OK;
 }
 
+// The split of the dense product over workgroups and LinearAlgebra.ishermitian(A) / opnorm(A, Inf) / count(!iszero, A) of the matrix
+// behind op.dense_ptr / op.lda: the tail of every dense creator and of a dense adjoint's refresh.
+static void dense_split_and_props(Ctx *ctx, Op &op) {
+  const int64_t n = op.n;
+  const int dtype = op.dtype;
+  const size_t esz = dtype_size(dtype);
+  const int64_t rows_per_block = dev::BLOCK * (16 / (int64_t)esz);
+  const int64_t gx = std::max<int64_t>(1, (n + rows_per_block - 1) / rows_per_block);
+  int split = (int)std::min<int64_t>(64, std::max<int64_t>(1, (1024 + gx - 1) / gx));
+  if (n < 64) split = 1;
+  op.gemv_split = split;
+  if (split > 1) op.gemv_scratch.alloc((size_t)split * n * esz);
+  if (n > 0) {
+    // LinearAlgebra.ishermitian(A) / opnorm(A, Inf) / count(!iszero, A) of the device copy (uploaded or the caller's): one
+    // pass of two small kernels at create time (setup cost), the same answer wherever the matrix came from
+    DevBuf scr(sizeof(double) * (size_t)split * (size_t)n), res(3 * sizeof(unsigned long long));
+    HIPCHECK(hipMemsetAsync(res.p, 0, res.bytes, ctx->stream));
+    dispatch_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      dev::dense_props<T>(ctx->stream, n, reinterpret_cast<const T *>(op.dense_ptr), op.lda, scr.as<double>(), split, res.as<unsigned long long>());
+    });
+    unsigned long long h[3] = {0, 0, 0};
+    HIPCHECK(hipMemcpyAsync(h, res.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(&op.opnorm_inf, &h[0], sizeof(double));
+    op.nnz = (int64_t)h[1];
+    op.ishermitian = h[2] == 0 ? 1 : 0;
+  }
+}
+
 int expv_mi_op_create_dense(expv_mi_ctx_t ctx, int dtype, int64_t n, const void *A, int64_t lda, int loc,
                             expv_mi_op_t *out) {
   return guarded(ctx, [&] {
@@ -2157,28 +2187,7 @@ int expv_mi_op_create_dense(expv_mi_ctx_t ctx, int dtype, int64_t n, const void 
       op->ishermitian = 0;
       op->opnorm_inf = 0.0;
     }
-    const int64_t rows_per_block = dev::BLOCK * (16 / (int64_t)esz);
-    const int64_t gx = std::max<int64_t>(1, (n + rows_per_block - 1) / rows_per_block);
-    int split = (int)std::min<int64_t>(64, std::max<int64_t>(1, (1024 + gx - 1) / gx));
-    if (n < 64) split = 1;
-    op->gemv_split = split;
-    if (split > 1) op->gemv_scratch.alloc((size_t)split * n * esz);
-    if (n > 0) {
-      // LinearAlgebra.ishermitian(A) / opnorm(A, Inf) / count(!iszero, A) of the device copy (uploaded or the caller's): one
-      // pass of two small kernels at create time (setup cost), the same answer wherever the matrix came from
-      DevBuf scr(sizeof(double) * (size_t)split * (size_t)n), res(3 * sizeof(unsigned long long));
-      HIPCHECK(hipMemsetAsync(res.p, 0, res.bytes, ctx->stream));
-      dispatch_dtype(dtype, [&](auto tag) {
-        using T = typename decltype(tag)::type;
-        dev::dense_props<T>(ctx->stream, n, reinterpret_cast<const T *>(op->dense_ptr), op->lda, scr.as<double>(), split, res.as<unsigned long long>());
-      });
-      unsigned long long h[3] = {0, 0, 0};
-      HIPCHECK(hipMemcpyAsync(h, res.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHECK(hipStreamSynchronize(ctx->stream));
-      std::memcpy(&op->opnorm_inf, &h[0], sizeof(double));
-      op->nnz = (int64_t)h[1];
-      op->ishermitian = h[2] == 0 ? 1 : 0;
-    }
+    dense_split_and_props(ctx, *op);
     ctx->adopt(&op->ctx);
     *out = op.release();
   });
@@ -2315,6 +2324,117 @@ int expv_mi_op_update_values(expv_mi_op_t op, const void *vals, int loc) {
       } else {
         op_update_values_T<T, V>(*op, vals, loc);
       }
+    });
+  });
+}
+
+// ---- the adjoint / transpose of an operator that exists (kernels: op_adjoint.hip) -----------------------------------------------
+static inline bool adjoint_conjugates(int how, int dtype) { return how == EXPV_MI_OP_ADJOINT && (dtype == EXPV_MI_C64 || dtype == EXPV_MI_C32); }
+
+// Sparse: the parent's stored entries -> (p[col], p[row]) keys -> the stable sort of the triplet path -> the sorted-row CSR32 arrays
+// of the transpose in the natural ordering and the values gathered behind them, then the tail of every device-born operator.
+static void create_adjoint_sparse(Ctx *ctx, Op &par, int how, expv_mi_op_t *out) {
+  const std::string who = "op_create_adjoint";
+  const auto t_begin = std::chrono::steady_clock::now();
+  hipStream_t s = ctx->stream;
+  const int64_t n = par.n, nnz = par.nnz;
+  const size_t vbytes = dtype_size(par.dtype);
+  DevBuf key[2], pay[2], hist, rep(sizeof(unsigned long long));
+  DevBuf ptr32(sizeof(int32_t) * (size_t)(n + 1)), idx32(sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1) + 16), pval(vbytes * (size_t)std::max<int64_t>(nnz, 1) + 16);
+  int passes = 0;
+  if (nnz > 0) {
+    for (int z = 0; z < 2; ++z) {
+      key[z].alloc(sizeof(unsigned long long) * (size_t)nnz + 16);
+      pay[z].alloc(sizeof(int32_t) * (size_t)nnz + 16);
+    }
+    hist.alloc(sizeof(uint32_t) * (size_t)dev::coo_hist_words(nnz));
+    dev::adj_keys(s, par.rowptr.as<int32_t>(), par.col.as<int32_t>(), par.perm ? par.perm->p.as<int32_t>() : nullptr, n, nnz,
+                  key[0].as<unsigned long long>(), pay[0].as<int32_t>());
+    unsigned long long *kp[2] = {key[0].as<unsigned long long>(), key[1].as<unsigned long long>()};
+    int32_t *pp[2] = {pay[0].as<int32_t>(), pay[1].as<int32_t>()};
+    passes = dev::coo_sort(s, n, nnz, kp, pp, hist.as<uint32_t>());      // (0 passes for n = 1: adj_keys wrote the identity payload)
+  }
+  DevBuf &skey = key[passes & 1], &src = pay[passes & 1];
+  dev::adj_pattern(s, skey.as<unsigned long long>(), n, nnz, ptr32.as<int32_t>(), idx32.as<int32_t>(), rep.as<unsigned long long>());
+  dev::adj_gather_values(s, (int)vbytes, adjoint_conjugates(how, par.dtype), par.val.p, src.as<int32_t>(), nnz, pval.p);
+  unsigned long long repeats = 0;
+  HIPCHECK(hipMemcpyAsync(&repeats, rep.p, sizeof(repeats), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  const auto t_ingest = std::chrono::steady_clock::now();
+  key[0].release();
+  key[1].release();
+  pay[(passes & 1) ^ 1].release();
+  hist.release();
+  // rows ascending by the sort; strictly ascending unless the parent repeats a coordinate
+  finish_sparse_device(ctx, who, false, par.dtype, n, nnz, ptr32, idx32, pval.p, repeats == 0, t_begin,
+                       (int64_t)std::chrono::duration<double, std::micro>(t_ingest - t_begin).count(),
+                       [&](Op &op) {      // what expv_mi_op_adjoint_refresh gathers through
+                         op.adj_how = how;
+                         if (nnz > 0) op.adj_src = std::move(src);
+                       },
+                       out);
+}
+
+// Dense: an owned packed copy of A' / transpose(A), then the property pass of a device-resident dense operator.
+static void create_adjoint_dense(Ctx *ctx, Op &par, int how, expv_mi_op_t *out) {
+  const int64_t n = par.n;
+  const size_t esz = dtype_size(par.dtype);
+  std::unique_ptr<expv_mi_op_s> op(new expv_mi_op_s());
+  op->ctx = ctx;
+  op->device = ctx->device;
+  op->dtype = par.dtype;
+  op->kind = OP_DENSE;
+  op->n = n;
+  op->dense.alloc((size_t)std::max<int64_t>(n * n, 1) * esz);
+  dev::adj_dense_transpose(ctx->stream, (int)esz, adjoint_conjugates(how, par.dtype), par.dense_ptr, par.lda, n, op->dense.p);
+  op->dense_ptr = op->dense.p;
+  op->lda = n;
+  op->nnz = n * n;
+  op->ishermitian = 0;
+  op->opnorm_inf = 0.0;
+  op->adj_how = how;
+  dense_split_and_props(ctx, *op);
+  ctx->adopt(&op->ctx);
+  *out = op.release();
+}
+
+int expv_mi_op_create_adjoint(expv_mi_op_t parent, int how, expv_mi_op_t *out) {
+  Ctx *ctx = parent ? parent->ctx : nullptr;
+  return guarded(ctx, [&] {
+    if (!out) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_adjoint: null output");
+    if (!parent || !ctx) fail(EXPV_MI_ARGUMENT_ERROR, "op_create_adjoint: null parent, or a parent whose context is gone");
+    if (how != EXPV_MI_OP_TRANSPOSE && how != EXPV_MI_OP_ADJOINT)
+      fail(EXPV_MI_ARGUMENT_ERROR, "op_create_adjoint: how must be EXPV_MI_OP_TRANSPOSE or EXPV_MI_OP_ADJOINT");
+    if (parent->kind == OP_CALLBACK) fail(EXPV_MI_UNSUPPORTED, "op_create_adjoint: a matrix-free operator has no adjoint callback");
+    ctx->use();
+    if (parent->kind == OP_DENSE) create_adjoint_dense(ctx, *parent, how, out);
+    else create_adjoint_sparse(ctx, *parent, how, out);
+  });
+}
+
+int expv_mi_op_adjoint_refresh(expv_mi_op_t adj, expv_mi_op_t parent) {
+  Ctx *ctx = adj ? adj->ctx : nullptr;
+  return guarded(ctx, [&] {
+    if (!adj || !parent) fail(EXPV_MI_ARGUMENT_ERROR, "op_adjoint_refresh: null operator");
+    if (!ctx || !parent->ctx) fail(EXPV_MI_ARGUMENT_ERROR, "op_adjoint_refresh: the context is gone");
+    if (adj->adj_how == 0) fail(EXPV_MI_ARGUMENT_ERROR, "op_adjoint_refresh: not created by op_create_adjoint");
+    if (parent->ctx != ctx) fail(EXPV_MI_ARGUMENT_ERROR, "op_adjoint_refresh: the two operators live on different contexts");
+    if (parent->kind != adj->kind || parent->dtype != adj->dtype || parent->n != adj->n || (adj->kind == OP_CSR && parent->nnz != adj->nnz))
+      fail(EXPV_MI_ARGUMENT_ERROR, "op_adjoint_refresh: the parent differs in kind, dtype, n or nnz from the operator this one was made from");
+    ctx->use();
+    const size_t esz = dtype_size(adj->dtype);
+    const bool conj = adjoint_conjugates(adj->adj_how, adj->dtype);
+    if (adj->kind == OP_DENSE) {
+      dev::adj_dense_transpose(ctx->stream, (int)esz, conj, parent->dense_ptr, parent->lda, adj->n, adj->dense.p);
+      dense_split_and_props(ctx, *adj);
+      return;
+    }
+    if (adj->nnz == 0) return;
+    if (!adj->adj_val.p) adj->adj_val.alloc(esz * (size_t)adj->nnz + 16);
+    dev::adj_gather_values(ctx->stream, (int)esz, conj, parent->val.p, adj->adj_src.as<int32_t>(), adj->nnz, adj->adj_val.p);
+    dispatch_host_dtype(adj->dtype, [&](auto tag) {
+      using V = typename decltype(tag)::type;
+      op_update_values_T<typename DevOf<V>::type, V>(*adj, adj->adj_val.p, EXPV_MI_DEVICE);
     });
   });
 }

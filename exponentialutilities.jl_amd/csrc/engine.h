@@ -338,6 +338,11 @@ struct Op {
   DevBuf sdia_table, sdia_val;
   std::vector<int64_t> sdia_base;      // the table once more on the host: a refresh from host data stages the in-matrix segments only
   std::vector<int32_t> sdia_off;
+  // adjoint-born (capi.hip: create_adjoint): EXPV_MI_OP_TRANSPOSE / EXPV_MI_OP_ADJOINT (0: not adjoint-born).  Sparse: adj_src[e] =
+  // the parent's STORED entry behind entry e of this operator's sorted-row arrays (int32, nnz of them: what a refresh gathers
+  // through) and, from the first refresh on, the buffer the gathered values go to.  Dense: `dense` is the owned packed copy.
+  int adj_how = 0;
+  DevBuf adj_src, adj_val;
   bool plan_cached = false;      // the ordering / patch plan came from the process-wide plan cache (capi.hip: OrderPlanCache)
   int64_t ring_sum = 0, ring_over128 = 0, ring_tiles = 0;      // sum of the ring lengths, tiles with a ring of more than 128 rows, tiles
   int ring_pad = 0;          // 0: no patch form

@@ -149,6 +149,21 @@ void dia_expand_pattern(hipStream_t s, const int32_t *off, int q, int64_t n, int
 // only elements at base[r] + i with 0 <= i + off[r] < n are read
 void dia_permute_values(hipStream_t s, int value_bytes, const void *data, const int64_t *base, const int32_t *off, int q, int64_t n,
                         int64_t nnz, void *out);
+// ---- the adjoint / transpose of an operator that exists, made from its stored arrays on the device (op_adjoint.hip; capi.hip:
+//      create_adjoint, expv_mi_op_adjoint_refresh).  Values move as raw 4- / 8- / 16-byte units; `conj` flips the sign bit of the
+//      imaginary part and is legal for the complex types only (value_bytes 8 = ComplexF32, 16 = ComplexF64) ----
+int adj_dense_tile(int value_bytes);             // side of the square tile the dense transposition stages in LDS
+// the parent's stored CSR32 arrays (p: its row ordering, position -> natural row; null: natural) -> key[e] = p[col] << 32 | p[row]
+// of stored entry e (the coordinate of the entry in the transpose) and pay[e] = e; both 16-byte aligned
+void adj_keys(hipStream_t s, const int32_t *rowptr, const int32_t *col, const int32_t *p, int64_t n, int64_t nnz, unsigned long long *key,
+              int32_t *pay);
+// sorted keys -> ptr32[n + 1], idx32[nnz] (16-byte aligned), *repeats (zeroed here) = positions whose key equals its predecessor's
+void adj_pattern(hipStream_t s, const unsigned long long *key, int64_t n, int64_t nnz, int32_t *ptr32, int32_t *idx32,
+                 unsigned long long *repeats);
+// out[e] = op(vals[src[e]]), e < nnz (out 16-byte aligned; vals aligned to min(value_bytes, 8))
+void adj_gather_values(hipStream_t s, int value_bytes, bool conj, const void *vals, const int32_t *src, int64_t nnz, void *out);
+// out[j + i n] = op(A[i + j lda]), i, j < n: column-major in, packed column-major out; rows n .. lda - 1 of A are not read
+void adj_dense_transpose(hipStream_t s, int value_bytes, bool conj, const void *A, int64_t lda, int64_t n, void *out);
 // dst[i + c ld_dst] = src[idx[i] + c ld_src], i < n, c < ncols: rows of `esz`-byte elements (4, 8 or 16) picked through an index
 // vector -- the permutation of a reordered operator applied to vectors on their way in (idx = perm) and out (idx = inverse)
 void gather_rows(hipStream_t s, size_t esz, void *dst, int64_t ld_dst, const void *src, int64_t ld_src, const int32_t *idx, int64_t n,

@@ -302,6 +302,39 @@ enum { EXPV_MI_DIA_ALIGN_COL = 0,    /* element (i, i+k) of diagonal k at data[d
        EXPV_MI_DIA_ALIGN_START = 2 };/* ... at data[d*ld + min(i, i+k)]: compact vectors, Julia's Tridiagonal(dl, d, du) / k => v pairs */
 int expv_mi_op_create_dia_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int ndiag, const int64_t *offsets_host,
                               const void *data, int64_t ld, int align, int loc, expv_mi_op_t *op);
+/* The operator of A' = conj(transpose(A)) (EXPV_MI_OP_ADJOINT) or of transpose(A) (EXPV_MI_OP_TRANSPOSE) of an operator that
+ * exists -- expv(t, A', b) of the reference, where A' is a lazy wrapper and mul! does the rest (arnoldi.jl:185): the call of an
+ * adjoint sensitivity and of a left eigenvector.  Here the result is an INDEPENDENT operator on the parent's context with its own
+ * storage, built on the device: the parent may be updated or destroyed afterwards, and neither the parent's values nor their
+ * transposed copies visit the host.  All four element types; for the real ones the two values of `how` give the same bits.
+ *   - Sparse parents, however they were created (host or device CSR / CSC, triplets, block arrays, stored diagonals; reordered,
+ *     patch form, irregular rows).  BY DEFINITION the result is the operator expv_mi_op_create_csr_loc would make, on the same
+ *     context, of the zero-based CSR32 arrays of A' (or transpose(A)) in the caller's natural ordering with every row in ascending
+ *     column order: the same planners, the plan cache keyed by the ADJOINT's pattern, its own reordering decision.  nnz equals the
+ *     parent's, stored zeros stay stored.  A parent stored as P A P' has its stored indices relabelled through P on the device
+ *     first.  Where the parent's rows repeat a coordinate the repeats stay separate entries, adjacent in the adjoint's row, in the
+ *     parent's stored order -- deterministic, but bit-equality with an operator made of arrays transposed elsewhere is not claimed
+ *     for such a parent.  Only the adjoint's PATTERN comes to the host (the planners live there), as for every device-born
+ *     operator: expv_mi_op_ingest_info reports out[0] = 1, out[1] = 4 (n + 1 + nnz), out[2] = 0 (rows sorted and free of
+ *     repeats), out[3 .. 5] as usual, out[6] = out[7] = 0.
+ *   - Dense parents: the result owns a packed (leading dimension n) column-major copy of A' / transpose(A), n^2 elements, and goes
+ *     through the property pass of expv_mi_op_create_dense(..., EXPV_MI_DEVICE).  Rows n .. lda - 1 of the parent are never read.
+ *   - Matrix-free parents: EXPV_MI_UNSUPPORTED -- there is no adjoint callback to call.
+ *   - Checks before any device work, EXPV_MI_ARGUMENT_ERROR "op_create_adjoint: ...", in this order: null output; null parent, or
+ *     a parent whose context is gone; `how` not one of the two.  *op is untouched on every failure.
+ *   - expv_mi_op_update_values on a sparse adjoint-born operator takes nnz values in the ADJOINT's own sorted-row order, which is
+ *     the column-major order of A (A's entries column after column, rows ascending inside a column).
+ * expv_mi_op_adjoint_refresh(adj, parent) re-reads the parent's CURRENT stored values on the device -- sparse: one gather through
+ * the map adj keeps (4 nnz bytes: adjoint entry e <- parent stored entry src[e]), conjugated for EXPV_MI_OP_ADJOINT; dense: the
+ * transposition again -- and refills adj through the path of expv_mi_op_update_values, so ishermitian and opnorm(A', Inf) =
+ * opnorm(A, 1) are re-evaluated.  The result is bit for bit what expv_mi_op_create_adjoint(parent) would make anew.
+ * EXPV_MI_ARGUMENT_ERROR "op_adjoint_refresh: ...": a null handle, adj not adjoint-born, another context, another kind, dtype, n
+ * or nnz.  A parent with the same counts but ANOTHER PATTERN than the one adj was made from is the caller's error and is not
+ * detected, as for expv_mi_op_update_values. */
+#define EXPV_MI_OP_TRANSPOSE 1   /* transpose(A): no conjugation */
+#define EXPV_MI_OP_ADJOINT   2   /* A' = conj(transpose(A)); real types: same bits as TRANSPOSE */
+int expv_mi_op_create_adjoint(expv_mi_op_t parent, int how, expv_mi_op_t *op);
+int expv_mi_op_adjoint_refresh(expv_mi_op_t adj, expv_mi_op_t parent);
 /* How a sparse operator came to be: out[0] 1 = created from device arrays (or triplets); out[1] bytes of pattern brought to the
  * host; out[2] bytes of VALUES brought to the host (0 when every row is sorted and free of duplicates); out[3] the whole creation
  * and out[4] the ingest kernels + status read-back (triplets: check, sort, compress and sums, by device events), in microseconds;

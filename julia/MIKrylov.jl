@@ -318,6 +318,43 @@ function patch_info(op::MIOperator)
     (patch_form = out[1] != 0, grid_row_length = out[2], tiles = out[3], longest_ring = out[4], mean_ring = out[3] > 0 ? out[5] / out[3] : 0.0)
 end
 MIOperator(A::SparseMatrixCSC{T}) where {T <: MIScalar} = MIOperator(SparseMatrixCSC{T, Int64}(A))      # (other index types: converted once)
+# A' and transpose(A) of an operator that exists (expv_mi_op_create_adjoint): the reference's expv(t, A', b), where A' is a lazy
+# wrapper and mul! does the rest (arnoldi.jl:185) -- the call of an adjoint sensitivity and of a left eigenvector.  Here the
+# result is a NEW, independent MIOperator built on the device from what A stores (sparse of any birth, or dense: an owned packed
+# copy); the values never visit the host, and A may be updated or finalised afterwards.  Every A' builds a new operator: keep it.
+# (A').opnorm_inf is opnorm(A, 1).  A matrix-free operator has no adjoint (Unsupported).
+const OP_TRANSPOSE, OP_ADJOINT = Cint(1), Cint(2)
+function adjoint_operator(A::MIOperator{T}, how::Cint) where {T}
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:expv_mi_op_create_adjoint, lib), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), A.h, how, r), ctx().h)
+    wrap_operator(T, r[])
+end
+Base.adjoint(A::MIOperator) = adjoint_operator(A, OP_ADJOINT)
+Base.transpose(A::MIOperator) = adjoint_operator(A, OP_TRANSPOSE)
+# The refresh: dest -- made by adjoint(parent) or transpose(parent), and staying what it was made as -- takes the CURRENT values of
+# parent (or of an operator of the same pattern) on the device; bit-equal to making it anew (expv_mi_op_adjoint_refresh).
+function LinearAlgebra.adjoint!(dest::MIOperator{T}, parent::MIOperator{T}) where {T}
+    check(ccall((:expv_mi_op_adjoint_refresh, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), dest.h, parent.h), ctx().h)
+    n, nz, hm, on, dt = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Cdouble}(0), Ref{Cint}(0)
+    check(ccall((:expv_mi_op_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Cint}, Ref{Cdouble}, Ref{Cint}), dest.h, n, nz, hm, on, dt), ctx().h)
+    dest.herm = hm[] != 0
+    dest.nnz = nz[]
+    dest.opnorm_inf = on[]
+    dest
+end
+# A lazy A' / transpose(A) of a host SparseMatrixCSC needs no device transposition: the parent's CSC arrays ARE the CSR arrays of
+# the transpose (columns sorted by row = rows sorted by column); the values are conjugated for an Adjoint.
+function MIOperator(A::Union{Adjoint{T, SparseMatrixCSC{T, Int64}}, Transpose{T, SparseMatrixCSC{T, Int64}}}) where {T <: MIScalar}
+    P = parent(A)
+    vals = A isa Adjoint ? conj(P.nzval) : P.nzval
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:expv_mi_op_create_csr, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ref{Ptr{Cvoid}}),
+                ctx().h, dtype(T), size(P, 1), P.colptr, P.rowval, vals, 8, 1, r), ctx().h)
+    wrap_operator(T, r[])
+end
+MIOperator(A::Adjoint{T, <:SparseMatrixCSC{T}}) where {T <: MIScalar} = MIOperator(adjoint(SparseMatrixCSC{T, Int64}(parent(A))))
+MIOperator(A::Transpose{T, <:SparseMatrixCSC{T}}) where {T <: MIScalar} = MIOperator(transpose(SparseMatrixCSC{T, Int64}(parent(A))))
 # A sparse matrix that is ALREADY on the device (test/gpu/gputests.jl:46: CuSparseMatrixCSR(A)): the three arrays of a CSR / CSC matrix
 # as device vectors -- the fields of a ROCSparseMatrixCSR (rowPtr, colVal, nzVal) or ROCSparseMatrixCSC (colPtr, rowVal, nzVal), wrapped
 # without a copy as MIArray{Ti, 1}(pointer, (length,), false); 1-based like every Julia sparse type.  The index arrays are checked on
