@@ -585,6 +585,11 @@ struct TaylorCall {
 void taylor_enqueue(Ctx *ctx, Op &op, double t_re, double t_im, const void *b_dev, int precision, int64_t max_matvecs, double opnorm,
                     TaylorCall &tc);
 void taylor_collect(Ctx *ctx, TaylorCall &tc, int64_t info[8], double dinfo[4]);
+// The operator has a form that a term kernel reads in the same pass as the vectors (SELL slots without overflow entries, or the
+// general diagonal form): tc.path = 1.  Otherwise a term is mul! and an update pass: tc.path = 2.  Everything else the four Taylor
+// sources share on the host -- the operator view, the term's launch bookkeeping, the closing launch, the info fill -- is templated on
+// the element type and lives in taylor_term.h (TaylorLaunch).
+bool taylor_fused(const Op &op);
 // The two parts of taylor_enqueue, for a caller that runs several vectors behind one plan (expv_taylor_block.hip).
 // taylor_shift_plan: the argument checks, mu / alpha (the one blocking read of a stored operator) and (m*, s) into tc; `head` is
 // taylor_head_bytes() of device memory whose first 128 bytes are a stage state, ready for taylor_run afterwards.  taylor_run: every

@@ -16,84 +16,22 @@
 //
 // Traffic per term: fused kernel (SELL slots without overflow, or the general diagonal form): the operator + x gather, x_i, F read,
 // y and F written -- the operator plus four vector streams.  Everything else: mul! (operator, x, y) + one update pass over x, y, F.
+//
+// This file holds the plan (mu, alpha, m*, s) and the host loop of the single call.  The term kernel k_taylor_term<T, FUSED>, its row
+// sweep and the launch setup shared with the phiv and grid entries are in taylor_term.h; the stage state, the closing kernel and the
+// element step that fixes the roundings of a term are in taylor_state.h.
 #include <cmath>
 #include <complex>
 #include <limits>
 
 #include "engine.h"
 #include "kernel_common.h"
-#include "sparse_rows.h"
 #include "taylor_state.h"
+#include "taylor_term.h"
 #include "taylor_theta.h"
 
 namespace expv_mi {
 namespace dev {
-
-// (the stage state TaylorState and the small helpers shared with the block kernels: taylor_state.h)
-
-// (taylor_arrive, the stopping test, TaylorTermArgs, the closing kernel and taylor_grid are shared with phiv_taylor.hip: taylor_state.h)
-
-// y_i = c (sum_k a_ik x_k - mu x_i), F_i += y_i, maxima, ticket: one term of the series in one pass over the operator
-template <class T>
-__global__ __launch_bounds__(BLOCK) void k_taylor_term_fused(TaylorTermArgs<T> a) {
-  if (taylor_skip(a.st)) return;
-  constexpr int N = Pack<T>::N;
-  constexpr int SH = 64 * N;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool alx = is_al16(a.x), aly = is_al16(a.y), alf = is_al16(a.F);
-  const int64_t nsl = (a.n + SH - 1) / SH;
-  double mv = 0.0, mf = 0.0;
-  unsigned nan = 0u;
-  for (int64_t slice = (int64_t)blockIdx.x * (BLOCK / 64) + wave; slice < nsl; slice += (int64_t)gridDim.x * (BLOCK / 64)) {
-    const int64_t i = slice * SH + (int64_t)lane * N;
-    const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);      // independent of the operator: in flight with its slots
-    Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
-    Pack<T> acc;
-    if (a.ndiag > 0) dia_rows<T>(a.dia_val, a.dia_ld, a.ndiag, a.dia_off, i, a.n, a.x, acc.v);
-    else sell_rows<T>(a.A, slice, lane, a.x, acc.v);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      ST<T>::nfma(acc.v[k], a.mu, xi.v[k]);
-      acc.v[k] = ST<T>::mul(a.c, acc.v[k]);
-      f.v[k] = ST<T>::add(f.v[k], acc.v[k]);
-      if (i + k < a.n) {      // (rows of the last pack beyond n hold what the padding slots gave: not part of the vector)
-        note_abs(abs_T(acc.v[k]), mv, nan, 1u);
-        note_abs(abs_T(f.v[k]), mf, nan, 2u);
-      }
-    }
-    st_pack_user(a.y, i, a.n, aly, acc);
-    st_pack_user(a.F, i, a.n, alf, f);
-  }
-  if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m, 0.0);
-}
-
-// the same behind mul!(y, A, x): y_i = c (y_i - mu x_i), F_i += y_i, maxima, ticket
-template <class T>
-__global__ __launch_bounds__(BLOCK) void k_taylor_term_update(TaylorTermArgs<T> a) {
-  if (taylor_skip(a.st)) return;
-  constexpr int N = Pack<T>::N;
-  const bool alx = is_al16(a.x), aly = is_al16(a.y), alf = is_al16(a.F);
-  double mv = 0.0, mf = 0.0;
-  unsigned nan = 0u;
-  for (int64_t i = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * N; i < a.n; i += (int64_t)gridDim.x * BLOCK * N) {
-    const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);
-    Pack<T> y = ld_pack_user(a.y, i, a.n, aly);
-    Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      ST<T>::nfma(y.v[k], a.mu, xi.v[k]);
-      y.v[k] = ST<T>::mul(a.c, y.v[k]);
-      f.v[k] = ST<T>::add(f.v[k], y.v[k]);
-      if (i + k < a.n) {
-        note_abs(abs_T(y.v[k]), mv, nan, 1u);
-        note_abs(abs_T(f.v[k]), mf, nan, 2u);
-      }
-    }
-    st_pack_user(a.y, i, a.n, aly, y);
-    st_pack_user(a.F, i, a.n, alf, f);
-  }
-  if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m, 0.0);
-}
 
 // mu = tr(A) / n and ||A - mu I||_inf of a stored operator, in two launches of one kernel over the arrays the operator keeps:
 // mode 0 sums the diagonal (per-workgroup partials, finished by the last workgroup in index order: the same bits every run) and
@@ -199,8 +137,6 @@ void taylor_params(int precision, double alpha, int *m_out, int64_t *s_out) {
 // ------------------------------------------------------------------------------------------
 // the call
 // ------------------------------------------------------------------------------------------
-static inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-
 size_t taylor_head_bytes() { return sizeof(dev::TaylorState) + sizeof(double) * 2 * dev::MAX_GRID; }
 
 // (m*, s) and tol for tc.alpha, and the max_matvecs refusal
@@ -243,9 +179,8 @@ static void taylor_shift_plan_T(Ctx *c, Op &op, std::complex<double> t, int prec
     HIPCHECK(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     ++tc.reads;
-    auto f64 = [](unsigned long long u) { double d; std::memcpy(&d, &u, 8); return d; };
-    mu = std::complex<double>(f64(h.mu_re), f64(h.mu_im));
-    anorm = (h.nanflags & 4ull) ? std::numeric_limits<double>::quiet_NaN() : f64(h.rowmax);
+    mu = std::complex<double>(f64_of(h.mu_re), f64_of(h.mu_im));
+    anorm = (h.nanflags & 4ull) ? std::numeric_limits<double>::quiet_NaN() : f64_of(h.rowmax);
   }
   tc.mu_re = mu.real();
   tc.mu_im = mu.imag();
@@ -258,58 +193,26 @@ static void taylor_shift_plan_T(Ctx *c, Op &op, std::complex<double> t, int prec
 // left); v0, v1 and F hold n elements each; b may be F itself.
 template <class T>
 static void taylor_run_T(Ctx *c, Op &op, std::complex<double> t, const void *b_dev, void *state, void *v0, void *v1, void *Fv, TaylorCall &tc) {
-  hipStream_t s = c->stream;
-  const int64_t n = op.n;
-  dev::TaylorState *st = reinterpret_cast<dev::TaylorState *>(state);
   T *V[2] = {reinterpret_cast<T *>(v0), reinterpret_cast<T *>(v1)};
-  T *F = reinterpret_cast<T *>(Fv);
-  const std::complex<double> mu(tc.mu_re, tc.mu_im);
-  const int m = tc.m;
   const int64_t ns = tc.s;
-  const double tol = tc.tol;
-
-  const bool fused = op.kind == OP_CSR && op.sell_ok && op.ovf_nseg == 0 && !op.cbf;
-  tc.path = fused ? 1 : 2;
-  dev::TaylorTermArgs<T> a{};
-  if (fused) {
-    a.A = dev::SellView<T>{op.sell_off.as<int64_t>(), op.sell_col.as<int32_t>(), op.sell_val.as<T>(), op.nslices};
-    if (op.gndiag > 0 && c->opt.dia) {
-      a.dia_val = op.gdia_ptr<T>(); a.dia_ld = op.gdia_ld; a.ndiag = op.gndiag; a.dia_off = op.gdia_off.as<int32_t>();
-    }
-  }
-  a.F = F; a.n = n; a.mu = taylor_scalar<T>(mu); a.tol = tol; a.m = m; a.st = st;
-  constexpr int SH = 64 * dev::Pack<T>::N;
-  const int g_fused = dev::taylor_grid((n + SH - 1) / SH, dev::BLOCK / 64);
-  const int g_elem = dev::taylor_grid(n, dev::BLOCK * dev::Pack<T>::N);
-  const std::complex<double> eta = taylor_stage_factor(mu, t, ns);
-  const bool scale = !(eta.real() == 1.0 && eta.imag() == 0.0);
-  auto close = [&](const T *src, T *v, int sc, int64_t stage) {
-    ProfScope ps(c, EXPV_MI_K_LINCOMB);
-    hipLaunchKernelGGL(dev::k_taylor_close<T>, dim3(g_elem), dim3(dev::BLOCK), 0, s, src, F, v, n, taylor_scalar<T>(eta), sc,
-                       (int)std::min<int64_t>(stage, 2147483646), (int)(stage + 1 < ns), 0.0, st);
-  };
+  const TaylorLaunch<T> L(c, op, tc, reinterpret_cast<T *>(Fv), reinterpret_cast<dev::TaylorState *>(state));
+  dev::TaylorTermArgs<T> a = L.args();
+  const std::complex<double> eta = taylor_stage_factor(std::complex<double>(tc.mu_re, tc.mu_im), t, ns);
   int p = 0;
-  close(reinterpret_cast<const T *>(b_dev), V[0], 0, -1);
+  L.close(reinterpret_cast<const T *>(b_dev), V[0], eta, -1, 0.0);
   for (int64_t stage = 0; stage < ns; ++stage) {
-    for (int j = 1; j <= m; ++j) {
+    for (int j = 1; j <= tc.m; ++j) {
       a.x = V[p]; a.y = V[1 - p]; a.j = j;
       a.c = taylor_scalar<T>(t / (double)ns / (double)j);
-      if (fused) {
-        ++c->cnt_opapply;
-        ProfScope ps(c, EXPV_MI_K_MATVEC);
-        hipLaunchKernelGGL(dev::k_taylor_term_fused<T>, dim3(g_fused), dim3(dev::BLOCK), 0, s, a);
-      } else {
-        op_apply_dev(op, a.x, a.y, nullptr, 0);
-        ProfScope ps(c, EXPV_MI_K_LINCOMB);
-        hipLaunchKernelGGL(dev::k_taylor_term_update<T>, dim3(g_elem), dim3(dev::BLOCK), 0, s, a);
-      }
-      ++tc.launches;
+      L.term(a, a.x, a.y, [](auto fused) { return dev::k_taylor_term<T, decltype(fused)::value>; });
       p ^= 1;
     }
-    close(F, V[p], scale ? 1 : 0, stage);
+    L.close(L.F, V[p], eta, stage, 0.0);
   }
   HIPCHECK(hipGetLastError());
 }
+
+bool taylor_fused(const Op &op) { return op.kind == OP_CSR && op.sell_ok && op.ovf_nseg == 0 && !op.cbf; }
 
 void taylor_check(const Op &op, double t_im, int precision, double opnorm) {
   (void)taylor_table(precision);
@@ -354,13 +257,7 @@ void taylor_collect(Ctx *c, TaylorCall &tc, int64_t info[8], double dinfo[4]) {
   HIPCHECK(hipMemcpyAsync(&h, tc.state, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   HIPCHECK(hipStreamSynchronize(c->stream));
   ++tc.reads;
-  double fnorm;
-  std::memcpy(&fnorm, &h.fnorm, 8);
-  if (info) {
-    info[0] = tc.m; info[1] = tc.s; info[2] = (int64_t)h.apps; info[3] = (int64_t)h.early; info[4] = tc.launches; info[5] = tc.reads;
-    info[6] = tc.path; info[7] = (int64_t)h.nf_stage;
-  }
-  if (dinfo) { dinfo[0] = tc.alpha; dinfo[1] = tc.mu_re; dinfo[2] = tc.mu_im; dinfo[3] = fnorm; }
+  taylor_fill_info(tc, h, info, dinfo);
 }
 
 }  // namespace expv_mi

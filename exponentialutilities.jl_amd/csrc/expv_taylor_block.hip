@@ -6,8 +6,9 @@
 // gather of a column index is one aligned P * sizeof(T) access.  Every column keeps its own stopping state -- maxima, c1, counters
 // as arrays of words, stopped / ended / NaN as bit masks -- in one state block per panel; a column that has stopped or ended is
 // masked (F written back unchanged, no maxima) until the stage's closing launch rebuilds its v.  The arithmetic of a column is the
-// single call's, operation for operation: acc summed over the slots / diagonals in ascending order, nfma(acc, mu, x_i), mul(c, acc),
-// F += acc -- so column k of the result is bit for bit what expv_mi_expv_taylor returns for column k of B.
+// single call's by construction: acc summed over the slots / diagonals in ascending order, then the element step the single kernel
+// calls too (taylor_step, taylor_state.h) -- so column k of the result is bit for bit what expv_mi_expv_taylor returns for column k of B.
+// The operator view, the fused predicate and the bookkeeping of a term launch are those of taylor_term.h.
 //
 // Synchronisation is that of expv_taylor.hip: agent-scope atomic maxima / OR, one ticket per launch, lane 0 of the last workgroup
 // to arrive runs the P tests and re-arms the state through L1-bypassing accesses.
@@ -23,8 +24,8 @@
 
 #include "engine.h"
 #include "kernel_common.h"
-#include "sparse_rows.h"
 #include "taylor_state.h"
+#include "taylor_term.h"
 
 namespace expv_mi {
 namespace dev {
@@ -133,14 +134,10 @@ __device__ __forceinline__ void block_rearm(TaylorBlockState *st) {
 __device__ __forceinline__ unsigned block_mask(const unsigned long long *a, const unsigned long long *b) {      // wave-uniform
   return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(ts_load(a) | (b ? ts_load(b) : 0ull)));
 }
-__device__ __forceinline__ double block_qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// (mul_as_single and term_sum, which hold the roundings of the single kernels: taylor_state.h, shared with expv_taylor_grid.hip)
 
 template <class T>
 struct BlockTermArgs {
-  SellView<T> A;                                  // SELL slots (ndiag == 0) ...
-  const T *dia_val; int64_t dia_ld; int ndiag; const int32_t *dia_off;      // ... or the general diagonal form
+  TaylorOpView<T> op;
   const T *x;                                     // v of the previous term, [row][P]
   T *y, *F;
   int64_t n;
@@ -150,7 +147,7 @@ struct BlockTermArgs {
   TaylorBlockState *st;
 };
 
-// k_taylor_term_fused for P columns: the lane <-> row mapping is the same (one 16-byte row pack of the operator per lane), the
+// k_taylor_term<T, true> for P columns: the lane <-> row mapping is the same (one 16-byte row pack of the operator per lane), the
 // operator's values and column indices are loaded once and used P times
 template <class T, int P>
 __global__ __launch_bounds__(BLOCK) void k_taylor_term_block(BlockTermArgs<T> a) {
@@ -170,8 +167,8 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_term_block(BlockTermArgs<T> a)
     const int64_t i = slice * SH + (int64_t)lane * N;      // (the work vectors are padded to whole slices: no tail path)
     T acc[N][P];
     BlockColumns<T, P> xs{a.x, acc};
-    if (a.ndiag > 0) dia_walk<T, InFlight<P>::Q>(a.dia_val, a.dia_ld, a.ndiag, a.dia_off, i, a.n, xs);
-    else sell_walk<T, InFlight<P>::Q>(a.A, slice, lane, xs);
+    if (a.op.ndiag > 0) dia_walk<T, InFlight<P>::Q>(a.op.dia_val, a.op.dia_ld, a.op.ndiag, a.op.dia_off, i, a.n, xs);
+    else sell_walk<T, InFlight<P>::Q>(a.op.A, slice, lane, xs);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
       const Row xi = *reinterpret_cast<const Row *>(a.x + (i + k) * P);
@@ -179,11 +176,8 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_term_block(BlockTermArgs<T> a)
       Row y;
 #pragma unroll
       for (int p = 0; p < P; ++p) {
-        T v = acc[k][p];
-        ST<T>::nfma(v, a.mu, xi.v[p]);
-        const T cv = mul_as_single(a.c, v);
-        const T fn = term_sum<T>(f.v[p], a.c, v, cv);
-        v = cv;
+        T v, fn;
+        taylor_step(acc[k][p], a.mu, xi.v[p], a.c, f.v[p], v, fn);
         y.v[p] = v;
         const bool live = !((off >> p) & 1u);      // (a masked column: F as it was, no maxima; its v is rebuilt when the stage closes)
         if (live) f.v[p] = fn;
@@ -202,8 +196,8 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_term_block(BlockTermArgs<T> a)
     unsigned long long stopped = ts_load(&st->stopped);
     for (int p = 0; p < P; ++p) {
       if ((off >> p) & 1u) continue;
-      const double c2 = ((nv >> p) & 1ull) ? block_qnan() : ts_loadf(&st->maxv[p]);
-      const double fn = ((nf >> p) & 1ull) ? block_qnan() : ts_loadf(&st->maxf[p]);
+      const double c2 = ((nv >> p) & 1ull) ? taylor_qnan() : ts_loadf(&st->maxv[p]);
+      const double fn = ((nf >> p) & 1ull) ? taylor_qnan() : ts_loadf(&st->maxf[p]);
       const double c1 = ts_loadf(&st->c1[p]);
       ts_store(&st->apps[p], ts_load(&st->apps[p]) + 1ull);
       if (c1 + c2 <= a.tol * fn) {
@@ -226,7 +220,7 @@ __device__ __forceinline__ void block_close_test(TaylorBlockState *st, unsigned 
   unsigned long long stopped = ts_load(&st->stopped), ended = ts_load(&st->ended);
   for (int p = 0; p < P; ++p) {
     if (!((cols >> p) & 1u)) continue;
-    const double fn = ((nf >> p) & 1ull) ? block_qnan() : ts_loadf(&st->maxf[p]);
+    const double fn = ((nf >> p) & 1ull) ? taylor_qnan() : ts_loadf(&st->maxf[p]);
     ts_storef(&st->c1[p], fn);
     ts_storef(&st->fnorm[p], fn);
     const bool finite = fn < __longlong_as_double(0x7ff0000000000000ll);
@@ -320,12 +314,6 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_block_copy(const T *__restrict
 
 namespace {
 
-inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-int grid_of(int64_t items, int per_block) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, dev::MAX_GRID));
-}
-double f64_of(unsigned long long u) { double d; std::memcpy(&d, &u, 8); return d; }
-
 struct BlockView {      // element (i, k) at p[i * rs + k * cs]
   char *p;
   int64_t rs, cs;
@@ -370,12 +358,9 @@ void run_panels(Ctx *c, Op &op, std::complex<double> t, BlockView Bv, BlockView 
   const int m = tc.m;
   const int64_t ns = tc.s;
   dev::BlockTermArgs<T> a{};
-  a.A = dev::SellView<T>{op.sell_off.as<int64_t>(), op.sell_col.as<int32_t>(), op.sell_val.as<T>(), op.nslices};
-  if (op.gndiag > 0 && c->opt.dia) {
-    a.dia_val = op.gdia_ptr<T>(); a.dia_ld = op.gdia_ld; a.ndiag = op.gndiag; a.dia_off = op.gdia_off.as<int32_t>();
-  }
+  a.op = taylor_op_view<T>(c, op);
   a.F = F; a.n = n; a.mu = taylor_scalar<T>(mu); a.tol = tc.tol; a.m = m;
-  const int g_term = grid_of(nsl, dev::BLOCK / 64), g_rows = grid_of(rows, dev::BLOCK);
+  const int g_term = dev::taylor_grid(nsl, dev::BLOCK / 64), g_rows = dev::taylor_grid(rows, dev::BLOCK);
   const std::complex<double> eta = taylor_stage_factor(mu, t, ns);
   const bool scale = !(eta.real() == 1.0 && eta.imag() == 0.0);
   const int32_t *perm = op.perm ? op.perm->p.as<int32_t>() : nullptr, *pinv = op.perm ? op.perm->pinv.as<int32_t>() : nullptr;
@@ -394,10 +379,8 @@ void run_panels(Ctx *c, Op &op, std::complex<double> t, BlockView Bv, BlockView 
       for (int j = 1; j <= m; ++j) {
         a.x = V[p]; a.y = V[1 - p]; a.j = j;
         a.c = taylor_scalar<T>(t / (double)ns / (double)j);
-        ++c->cnt_opapply;
-        ProfScope ps(c, EXPV_MI_K_MATVEC);
-        hipLaunchKernelGGL((dev::k_taylor_term_block<T, P>), dim3(g_term), dim3(dev::BLOCK), 0, s, a);
-        ++tc.launches;
+        taylor_term_launch(c, op, tc, true, a.x, a.y,
+                           [&] { hipLaunchKernelGGL((dev::k_taylor_term_block<T, P>), dim3(g_term), dim3(dev::BLOCK), 0, s, a); });
         p ^= 1;
       }
       ProfScope ps(c, EXPV_MI_K_LINCOMB);
@@ -479,7 +462,7 @@ void taylor_block_copy(Ctx *c, Op &op, const void *src, int64_t srs, int64_t scs
   dispatch_dtype(op.dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     for (int k0 = 0; k0 < ncols; k0 += 65535) {      // (gridDim.y <= 65535)
-      const dim3 g((unsigned)grid_of(n, dev::BLOCK), (unsigned)std::min(ncols - k0, 65535));
+      const dim3 g((unsigned)dev::taylor_grid(n, dev::BLOCK), (unsigned)std::min(ncols - k0, 65535));
       hipLaunchKernelGGL(dev::k_taylor_block_copy<T>, g, dim3(dev::BLOCK), 0, c->stream, reinterpret_cast<const T *>(src) + (int64_t)k0 * scs, srs, scs,
                          reinterpret_cast<T *>(dst) + (int64_t)k0 * dcs, drs, dcs, idx, n);
     }
@@ -513,8 +496,7 @@ void taylor_block_run(Ctx *c, Op &op, double t_re, double t_im, const void *B, i
     const std::function<void()> before_wait = [&] {
       if (w_loc == EXPV_MI_HOST) copy_block(s, W, ldw, wstage.p, ld_compact[w_layout], w_layout, n, ncols, esz, hipMemcpyDeviceToHost);
     };
-    const bool fused = op.kind == OP_CSR && op.sell_ok && op.ovf_nseg == 0 && !op.cbf;
-    if (fused && ncols >= 2) {
+    if (taylor_fused(op) && ncols >= 2) {
       tc.path = 1;
       dispatch_dtype(op.dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;

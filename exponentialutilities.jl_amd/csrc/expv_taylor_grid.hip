@@ -7,8 +7,8 @@
 //   otherwise  an INTERIOR output of stage i_k: the terms v_j = (hA)^j F / j! of the stage are all there, and
 //              exp(rho h A) F = sum_j rho^j v_j, so G_k = F + sum_j d_kj v_j with d_kj = d_k,j-1 rho_k (double, rounded to the
 //              operator's real type, passed by value), closed with G_k <- exp(mu rho_k h) G_k.
-// F and v run as in expv_taylor.hip, operation for operation (mul_as_single / term_sum, taylor_state.h): every output with r_k = R is
-// bit for bit what the single call returns for T.  No output costs a pass over the operator: the interior outputs of a stage live
+// F and v run through the row sweep and the element step of the single call (taylor_sweep, taylor_term.h; taylor_step,
+// taylor_state.h) with the panel as the sweep's policy: every output with r_k = R is bit for bit what the single call returns for T.  No output costs a pass over the operator: the interior outputs of a stage live
 // in panels of P in {2, 4, 8} interleaved columns [row][P]; the first panel is updated in the epilogue of the term kernel, every
 // further one by an accumulate-only launch that reads v_j once for its panel.
 //
@@ -31,8 +31,8 @@
 
 #include "engine.h"
 #include "kernel_common.h"
-#include "sparse_rows.h"
 #include "taylor_state.h"
+#include "taylor_term.h"
 
 namespace expv_mi {
 namespace dev {
@@ -64,7 +64,6 @@ struct __attribute__((aligned(16))) GridRow {
   T v[P];
 };
 
-__device__ __forceinline__ double grid_qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
 __device__ __forceinline__ unsigned grid_uniform(unsigned long long v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v); }
 
 // A running maximum of absolute values that KEEPS a NaN: a non-negative double orders like its bit pattern, and the pattern of a
@@ -197,7 +196,7 @@ __device__ __forceinline__ void grid_panel_test(TaylorGridPanel *ps, TaylorGridS
   for (int p = 0; p < P; ++p) {
     if (!((stopped >> p) & 1ull)) {
       const double c2 = (double)d[p] * vmax;
-      const double gn = ((ng >> p) & 1ull) ? grid_qnan() : ts_loadf(&ps->maxg[p]);
+      const double gn = ((ng >> p) & 1ull) ? taylor_qnan() : ts_loadf(&ps->maxg[p]);
       const double c1 = ts_loadf(j == 1 ? &gs->c1 : &ps->c1[p]);
       ts_store(&ps->terms[p], ts_load(&ps->terms[p]) + 1ull);
       if (c1 + c2 <= tol * gn) {
@@ -215,27 +214,22 @@ __device__ __forceinline__ void grid_panel_test(TaylorGridPanel *ps, TaylorGridS
   ts_store(&ps->ticket, 0ull);
 }
 
-// lane 0 of the last workgroup of a term launch: F's test (taylor_term_test, unless F has stopped), then the first panel's
+// lane 0 of the last workgroup of a term launch: |v_j|_inf for the panels, F's test (unless F has stopped), then the first panel's
 template <class T, int P>
 __device__ __forceinline__ void grid_term_test(const GridTermArgs<T> &ga, const typename ST<T>::real_t *d, bool fstop, bool pan) {
   const TaylorTermArgs<T> &a = ga.t;
   TaylorState *st = a.st;
   TaylorGridStage *gs = ga.gs;
   const unsigned long long nan = ts_load(&st->nanflags);
-  const double c2 = (nan & 1ull) ? grid_qnan() : ts_loadf(&st->maxv);
+  const double c2 = taylor_vmax(st, nan);
   if (a.j == 1) ts_store(&gs->c1, ts_load(&st->c1));      // (before F's test replaces it)
   ts_storef(&gs->vmax, c2);
   ts_store(&st->apps, ts_load(&st->apps) + 1ull);
   if (!fstop) {
-    const double fn = (nan & 2ull) ? grid_qnan() : ts_loadf(&st->maxf);
+    const double fn = taylor_fnorm(st, nan);
     const double c1 = ts_loadf(&st->c1);
     ts_store(&gs->fterms, ts_load(&gs->fterms) + 1ull);
-    if (c1 + c2 <= a.tol * fn) {
-      ts_store(&st->stopped, 1ull);
-      if (a.j < a.m) ts_store(&st->early, ts_load(&st->early) + 1ull);
-    } else {
-      ts_storef(&st->c1, c2);
-    }
+    taylor_f_test(st, c1, c2, fn, a.tol, a.j, a.m);
   }
   if (pan) grid_panel_test<T, P>(ga.ps, gs, d, a.tol, a.j);
   taylor_rearm(st);
@@ -254,100 +248,39 @@ __device__ __forceinline__ bool grid_skip(const TaylorState *st, TaylorGridStage
   return ts_load(&gs->live) == 0ull;
 }
 
-// k_taylor_term_fused + the first panel of the stage's interior outputs
+// The first panel of the stage's interior outputs as a policy of taylor_sweep: F masked once it has stopped, and the panel's rows
+// updated behind the stores of y and F.
 template <class T, int P>
+struct GridPanel {
+  const GridTermArgs<T> &ga;
+  const typename ST<T>::real_t *d;      // the panel's coefficients, in LDS
+  const bool fstop;
+  const unsigned off;                   // the panel's stopped columns
+  const bool pan;                       // a column of the panel is live
+  double mg[P];
+  __device__ __forceinline__ void rows(int64_t i, const Pack<T> &xi, const Pack<T> &y) {
+    if (!pan) return;
+#pragma unroll
+    for (int k = 0; k < Pack<T>::N; ++k)
+      if (i + k < ga.t.n) grid_panel_row<T, P>(ga.G, i + k, ga.t.j == 1, xi.v[k], y.v[k], d, off, mg);
+  }
+};
+
+// k_taylor_term + the first panel of the stage's interior outputs
+template <class T, int P, bool FUSED>
 __global__ __launch_bounds__(BLOCK) void k_taylor_term_grid(GridTermArgs<T> ga) {
   const TaylorTermArgs<T> &a = ga.t;
   if (grid_skip(a.st, ga.gs, a.j)) return;
   constexpr unsigned ALL = (1u << P) - 1u;
-  constexpr int N = Pack<T>::N;
-  constexpr int SH = 64 * N;
   const bool fstop = grid_uniform(ts_load(&a.st->stopped)) != 0u;
   const unsigned off = grid_uniform(ts_load(&ga.ps->stopped)) & ALL;
-  const bool pan = off != ALL;
   __shared__ typename ST<T>::real_t d_s[P];
   grid_coef_to_lds<T, P>(d_s, ga.co);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool alx = is_al16(a.x), aly = is_al16(a.y), alf = is_al16(a.F);
-  const int64_t nsl = (a.n + SH - 1) / SH;
-  double mv = 0.0, mf = 0.0, mg[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) mg[p] = 0.0;
+  GridPanel<T, P> x{ga, d_s, fstop, off, off != ALL, {}};
+  double mv = 0.0, mf = 0.0;
   unsigned nan = 0u;
-  for (int64_t slice = (int64_t)blockIdx.x * (BLOCK / 64) + wave; slice < nsl; slice += (int64_t)gridDim.x * (BLOCK / 64)) {
-    const int64_t i = slice * SH + (int64_t)lane * N;
-    const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);
-    Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
-    Pack<T> acc;
-    if (a.ndiag > 0) dia_rows<T>(a.dia_val, a.dia_ld, a.ndiag, a.dia_off, i, a.n, a.x, acc.v);
-    else sell_rows<T>(a.A, slice, lane, a.x, acc.v);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      T v = acc.v[k];
-      ST<T>::nfma(v, a.mu, xi.v[k]);
-      const T cv = mul_as_single(a.c, v);
-      const T fn = term_sum<T>(f.v[k], a.c, v, cv);
-      acc.v[k] = cv;
-      if (!fstop) f.v[k] = fn;      // (F has stopped: written back as it is, no maxima)
-      if (i + k < a.n) {
-        note_abs(abs_T(cv), mv, nan, 1u);
-        if (!fstop) note_abs(abs_T(fn), mf, nan, 2u);
-      }
-    }
-    st_pack_user(a.y, i, a.n, aly, acc);
-    st_pack_user(a.F, i, a.n, alf, f);
-    if (pan) {
-#pragma unroll
-      for (int k = 0; k < N; ++k)
-        if (i + k < a.n) grid_panel_row<T, P>(ga.G, i + k, a.j == 1, xi.v[k], acc.v[k], d_s, off, mg);
-    }
-  }
-  if (grid_arrive<P>(a.st, ga.ps, &a.st->ticket, mv, mf, nan, mg) && threadIdx.x == 0) grid_term_test<T, P>(ga, d_s, fstop, pan);
-}
-
-// the same behind mul!(y, A, x)
-template <class T, int P>
-__global__ __launch_bounds__(BLOCK) void k_taylor_term_update_grid(GridTermArgs<T> ga) {
-  const TaylorTermArgs<T> &a = ga.t;
-  if (grid_skip(a.st, ga.gs, a.j)) return;
-  constexpr unsigned ALL = (1u << P) - 1u;
-  constexpr int N = Pack<T>::N;
-  const bool fstop = grid_uniform(ts_load(&a.st->stopped)) != 0u;
-  const unsigned off = grid_uniform(ts_load(&ga.ps->stopped)) & ALL;
-  const bool pan = off != ALL;
-  __shared__ typename ST<T>::real_t d_s[P];
-  grid_coef_to_lds<T, P>(d_s, ga.co);
-  const bool alx = is_al16(a.x), aly = is_al16(a.y), alf = is_al16(a.F);
-  double mv = 0.0, mf = 0.0, mg[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) mg[p] = 0.0;
-  unsigned nan = 0u;
-  for (int64_t i = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * N; i < a.n; i += (int64_t)gridDim.x * BLOCK * N) {
-    const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);
-    Pack<T> y = ld_pack_user(a.y, i, a.n, aly);
-    Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      T v = y.v[k];
-      ST<T>::nfma(v, a.mu, xi.v[k]);
-      const T cv = mul_as_single(a.c, v);
-      const T fn = term_sum<T>(f.v[k], a.c, v, cv);
-      y.v[k] = cv;
-      if (!fstop) f.v[k] = fn;
-      if (i + k < a.n) {
-        note_abs(abs_T(cv), mv, nan, 1u);
-        if (!fstop) note_abs(abs_T(fn), mf, nan, 2u);
-      }
-    }
-    st_pack_user(a.y, i, a.n, aly, y);
-    st_pack_user(a.F, i, a.n, alf, f);
-    if (pan) {
-#pragma unroll
-      for (int k = 0; k < N; ++k)
-        if (i + k < a.n) grid_panel_row<T, P>(ga.G, i + k, a.j == 1, xi.v[k], y.v[k], d_s, off, mg);
-    }
-  }
-  if (grid_arrive<P>(a.st, ga.ps, &a.st->ticket, mv, mf, nan, mg) && threadIdx.x == 0) grid_term_test<T, P>(ga, d_s, fstop, pan);
+  taylor_sweep<T, FUSED>(a, x, mv, mf, nan);
+  if (grid_arrive<P>(a.st, ga.ps, &a.st->ticket, mv, mf, nan, x.mg) && threadIdx.x == 0) grid_term_test<T, P>(ga, d_s, fstop, x.pan);
 }
 
 template <class T>
@@ -466,12 +399,6 @@ void taylor_grid_plan(int64_t s, const double *r, int nt, int64_t *stage, double
 
 namespace {
 
-inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-int grid_of(int64_t items, int per_block) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, dev::MAX_GRID));
-}
-double f64_of(unsigned long long u) { double d; std::memcpy(&d, &u, 8); return d; }
-
 struct GridStagePlan {      // a stage that has outputs
   int64_t stage;
   std::vector<int> interior, ends;
@@ -577,32 +504,16 @@ void grid_run_T(Ctx *c, Op &op, std::complex<double> t, const double *r, int nt,
   }
   HIPCHECK(hipMemcpyAsync(states, init.data(), sbytes, hipMemcpyHostToDevice, s));
 
-  const bool fused = op.kind == OP_CSR && op.sell_ok && op.ovf_nseg == 0 && !op.cbf;
-  tc.path = fused ? 1 : 2;
+  const TaylorLaunch<T> L(c, op, tc, F, st);
   dev::GridTermArgs<T> ga{};
   dev::TaylorTermArgs<T> &a = ga.t;
-  if (fused) {
-    a.A = dev::SellView<T>{op.sell_off.as<int64_t>(), op.sell_col.as<int32_t>(), op.sell_val.as<T>(), op.nslices};
-    if (op.gndiag > 0 && c->opt.dia) {
-      a.dia_val = op.gdia_ptr<T>(); a.dia_ld = op.gdia_ld; a.ndiag = op.gndiag; a.dia_off = op.gdia_off.as<int32_t>();
-    }
-  }
-  a.F = F; a.n = n; a.mu = taylor_scalar<T>(mu); a.tol = tc.tol; a.m = m; a.st = st;
-  constexpr int SH = 64 * dev::Pack<T>::N;
-  const int g_fused = dev::taylor_grid((n + SH - 1) / SH, dev::BLOCK / 64);
-  const int g_elem = dev::taylor_grid(n, dev::BLOCK * dev::Pack<T>::N);
-  const int g_rows = grid_of(n, dev::BLOCK);
+  a = L.args();
+  const int g_rows = dev::taylor_grid(n, dev::BLOCK);
   const std::complex<double> h = Tt / (double)ns;
   const std::complex<double> eta = taylor_stage_factor(mu, Tt, ns);
-  const bool scale = !(eta.real() == 1.0 && eta.imag() == 0.0);
   const int32_t *pinv = op.perm ? op.perm->pinv.as<int32_t>() : nullptr;
   int64_t accum_launches = 0;
 
-  auto close = [&](const T *src, T *v, int sc, int64_t stg) {
-    ProfScope ps(c, EXPV_MI_K_LINCOMB);
-    hipLaunchKernelGGL(dev::k_taylor_close<T>, dim3(g_elem), dim3(dev::BLOCK), 0, s, src, F, v, n, taylor_scalar<T>(eta), sc,
-                       (int)std::min<int64_t>(stg, 2147483646), (int)(stg + 1 < ns), 0.0, st);
-  };
   // the outputs `cols` from a vector (b or F), 8 per launch; factor[k]: what output k is multiplied by
   auto out_vector = [&](const T *src, const std::vector<int> &cols, const std::vector<std::complex<double>> *factor) {
     for (size_t k0 = 0; k0 < cols.size(); k0 += dev::GPANEL) {
@@ -624,7 +535,7 @@ void grid_run_T(Ctx *c, Op &op, std::complex<double> t, const double *r, int nt,
   out_vector(b_dev, from_b, nullptr);
   int p = 0;
   size_t next = 0;
-  close(b_dev, V[0], 0, -1);
+  L.close(b_dev, V[0], eta, -1, 0.0);
   for (int64_t stg = 0; stg < ns; ++stg) {
     GridStagePlan *pl = (next < plans.size() && plans[next].stage == stg) ? &plans[next++] : nullptr;
     const int q = (pl && m > 0) ? (int)pl->interior.size() : 0;
@@ -643,18 +554,11 @@ void grid_run_T(Ctx *c, Op &op, std::complex<double> t, const double *r, int nt,
       a.x = V[p]; a.y = V[1 - p]; a.j = j;
       a.c = taylor_scalar<T>(Tt / (double)ns / (double)j);
       for (int k = 0; k < q; ++k) d[k] *= rho[pl->interior[k]];
-      if (!fused) op_apply_dev(op, a.x, a.y, nullptr, 0);
-      else ++c->cnt_opapply;
-      {
-        ga.G = reinterpret_cast<T *>(panels); ga.ps = pst; ga.gs = gs; ga.co = coef(0);
-        ProfScope ps(c, fused ? EXPV_MI_K_MATVEC : EXPV_MI_K_LINCOMB);
-        with_panel<T>(q > 0 ? width(0) : panel_width<T>(1), [&](auto ptag) {
-          constexpr int P = decltype(ptag)::value;
-          if (fused) hipLaunchKernelGGL((dev::k_taylor_term_grid<T, P>), dim3(g_fused), dim3(dev::BLOCK), 0, s, ga);
-          else hipLaunchKernelGGL((dev::k_taylor_term_update_grid<T, P>), dim3(g_elem), dim3(dev::BLOCK), 0, s, ga);
-        });
-      }
-      ++tc.launches;
+      ga.G = reinterpret_cast<T *>(panels); ga.ps = pst; ga.gs = gs; ga.co = coef(0);
+      with_panel<T>(q > 0 ? width(0) : panel_width<T>(1), [&](auto ptag) {
+        constexpr int P = decltype(ptag)::value;
+        L.term(ga, a.x, a.y, [](auto fused) { return dev::k_taylor_term_grid<T, P, decltype(fused)::value>; });
+      });
       for (int pi = 1; pi < np; ++pi) {
         dev::GridAccumArgs<T> aa{};
         aa.x = a.x; aa.y = a.y; aa.G = reinterpret_cast<T *>(panels + (size_t)pi * pbytes); aa.n = n; aa.co = coef(pi); aa.tol = tc.tol; aa.j = j;
@@ -690,7 +594,7 @@ void grid_run_T(Ctx *c, Op &op, std::complex<double> t, const double *r, int nt,
       for (int k : pl->interior) z.push_back(std::exp(mu * (r[k] * t)));
       out_vector(b_dev, pl->interior, &z);
     }
-    close(F, V[p], scale ? 1 : 0, stg);
+    L.close(F, V[p], eta, stg, 0.0);
     if (pl) out_vector(F, pl->ends, nullptr);
   }
   HIPCHECK(hipGetLastError());
@@ -702,11 +606,8 @@ void grid_run_T(Ctx *c, Op &op, std::complex<double> t, const double *r, int nt,
   HIPCHECK(hipMemcpyAsync(hs.data(), states, sbytes, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
   ++tc.reads;
-  if (info) {
-    info[0] = m; info[1] = ns; info[2] = (int64_t)hst.apps; info[3] = (int64_t)hst.early; info[4] = tc.launches; info[5] = tc.reads;
-    info[6] = tc.path; info[7] = (int64_t)hst.nf_stage; info[8] = accum_launches; info[9] = qmax;
-  }
-  if (dinfo) { dinfo[0] = tc.alpha; dinfo[1] = tc.mu_re; dinfo[2] = tc.mu_im; dinfo[3] = f64_of(hst.fnorm); }
+  taylor_fill_info(tc, hst, info, dinfo);
+  if (info) { info[8] = accum_launches; info[9] = qmax; }
   if (col_info) {
     for (int k = 0; k < nt; ++k) { col_info[3 * k] = stage[k]; col_info[3 * k + 1] = 0; col_info[3 * k + 2] = kind[k]; }
     for (const auto &pl : plans) {

@@ -15,7 +15,8 @@
 // terms.  The norm behind (m*, s) is that of diag(I, nu) A~ diag(I, 1 / nu) - mu I with nu = 2^-ceil(log2 max_i sum_{k>=1} |u_k[i]|)
 // (the paper's scaling against over-scaling: the similarity changes nothing but the norm), mu = tr(A) / (n + p).
 //
-// One column (p = 0) is exp(tA) u_0: it runs the single-vector loop of expv_taylor.hip itself, plan included.
+// One column (p = 0) is exp(tA) u_0: it runs the single-vector loop of expv_taylor.hip itself, plan included.  With p >= 1 the term
+// kernel k_phiv_term below has loops of its own on the shared element arithmetic; the host side is TaylorLaunch (taylor_term.h).
 #include <cmath>
 #include <complex>
 #include <cstring>
@@ -23,8 +24,8 @@
 
 #include "engine.h"
 #include "kernel_common.h"
-#include "sparse_rows.h"
 #include "taylor_state.h"
+#include "taylor_term.h"
 
 namespace expv_mi {
 
@@ -69,73 +70,72 @@ __device__ __forceinline__ void phiv_add(const PhivTermArgs<T> &a, const Pack<T>
     if ((a.mask >> k) & 1u) ST<T>::fma_(y, a.g[k], u[k].v[r]);
 }
 
-// k_taylor_term_fused + the rank-p add: y_i = c (sum_k a_ik x_k - mu x_i) + sum_k g_k u_k[i], F_i += y_i, maxima, ticket.  The packs
-// of the needed columns are issued with the x_i and F loads, ahead of the operator's slots.
-template <class T>
-__global__ __launch_bounds__(BLOCK) void k_phiv_term_fused(PhivTermArgs<T> pa) {
-  const TaylorTermArgs<T> &a = pa.t;
-  if (taylor_skip(a.st)) return;
-  constexpr int N = Pack<T>::N;
-  constexpr int SH = 64 * N;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool alx = is_al16(a.x), aly = is_al16(a.y), alf = is_al16(a.F);
-  const int64_t nsl = (a.n + SH - 1) / SH;
-  double mv = 0.0, mf = 0.0;
-  unsigned nan = 0u;
-  for (int64_t slice = (int64_t)blockIdx.x * (BLOCK / 64) + wave; slice < nsl; slice += (int64_t)gridDim.x * (BLOCK / 64)) {
-    const int64_t i = slice * SH + (int64_t)lane * N;
-    const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);
-    Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
-    Pack<T> u[PHIV_TAYLOR_PMAX];
-    if (pa.mask) phiv_load<T>(pa, i, u);
-    Pack<T> acc;
-    if (a.ndiag > 0) dia_rows<T>(a.dia_val, a.dia_ld, a.ndiag, a.dia_off, i, a.n, a.x, acc.v);
-    else sell_rows<T>(a.A, slice, lane, a.x, acc.v);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      ST<T>::nfma(acc.v[k], a.mu, xi.v[k]);
-      acc.v[k] = ST<T>::mul(a.c, acc.v[k]);
-      if (pa.mask) phiv_add<T>(pa, u, k, acc.v[k]);
-      f.v[k] = ST<T>::add(f.v[k], acc.v[k]);
-      if (i + k < a.n) {
-        note_abs(abs_T(acc.v[k]), mv, nan, 1u);
-        note_abs(abs_T(f.v[k]), mf, nan, 2u);
-      }
-    }
-    st_pack_user(a.y, i, a.n, aly, acc);
-    st_pack_user(a.F, i, a.n, alf, f);
-  }
-  if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m, pa.tail);
-}
-
-// the same behind mul!(y, A, x): y_i = c (y_i - mu x_i) + sum_k g_k u_k[i], F_i += y_i, maxima, ticket
-template <class T>
-__global__ __launch_bounds__(BLOCK) void k_phiv_term_update(PhivTermArgs<T> pa) {
+// k_taylor_term + the rank-p add: y_i = c ((A x)_i - mu x_i) + sum_k g_k u_k[i], F_i += y_i, maxima, ticket, and the test with the
+// tail as a floor.  The packs of the needed columns are issued with the x_i and F loads, ahead of the operator's slots.
+// The roundings: y = c v by the first half of the element step (taylor_product, taylor_state.h), then one fused multiply-add chain
+// per needed column in ascending k, then the PLAIN sum F + y for every element type -- also when the mask is empty: a term of phiv
+// never fuses c v into F as the real exp(tA)b step does.
+// This kernel does NOT go through taylor_sweep (taylor_term.h): it keeps the scalar registers short (g, the column alignments and
+// the mask bits live there), and with its rows or even one element behind a function of its own the compiler spills 2 .. 6 more of
+// them (its resource report; profiles/taylor_term_regs.txt).  So the two loops stand here as text, on the shared small pieces.
+template <class T, bool FUSED>
+__global__ __launch_bounds__(BLOCK) void k_phiv_term(PhivTermArgs<T> pa) {
   const TaylorTermArgs<T> &a = pa.t;
   if (taylor_skip(a.st)) return;
   constexpr int N = Pack<T>::N;
   const bool alx = is_al16(a.x), aly = is_al16(a.y), alf = is_al16(a.F);
   double mv = 0.0, mf = 0.0;
   unsigned nan = 0u;
-  for (int64_t i = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * N; i < a.n; i += (int64_t)gridDim.x * BLOCK * N) {
-    const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);
-    Pack<T> y = ld_pack_user(a.y, i, a.n, aly);
-    Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
-    Pack<T> u[PHIV_TAYLOR_PMAX];
-    if (pa.mask) phiv_load<T>(pa, i, u);
+  if constexpr (FUSED) {
+    constexpr int SH = 64 * N;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t nsl = (a.n + SH - 1) / SH;
+    for (int64_t slice = (int64_t)blockIdx.x * (BLOCK / 64) + wave; slice < nsl; slice += (int64_t)gridDim.x * (BLOCK / 64)) {
+      const int64_t i = slice * SH + (int64_t)lane * N;
+      const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);
+      Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
+      Pack<T> u[PHIV_TAYLOR_PMAX];
+      if (pa.mask) phiv_load<T>(pa, i, u);
+      Pack<T> acc;
+      if (a.op.ndiag > 0) dia_rows<T>(a.op.dia_val, a.op.dia_ld, a.op.ndiag, a.op.dia_off, i, a.n, a.x, acc.v);
+      else sell_rows<T>(a.op.A, slice, lane, a.x, acc.v);
 #pragma unroll
-    for (int k = 0; k < N; ++k) {
-      ST<T>::nfma(y.v[k], a.mu, xi.v[k]);
-      y.v[k] = ST<T>::mul(a.c, y.v[k]);
-      if (pa.mask) phiv_add<T>(pa, u, k, y.v[k]);
-      f.v[k] = ST<T>::add(f.v[k], y.v[k]);
-      if (i + k < a.n) {
-        note_abs(abs_T(y.v[k]), mv, nan, 1u);
-        note_abs(abs_T(f.v[k]), mf, nan, 2u);
+      for (int k = 0; k < N; ++k) {
+        T v, y;
+        taylor_product(acc.v[k], a.mu, xi.v[k], a.c, v, y);
+        if (pa.mask) phiv_add<T>(pa, u, k, y);
+        acc.v[k] = y;
+        f.v[k] = add_as_written(f.v[k], y);
+        if (i + k < a.n) {
+          note_abs(abs_T(y), mv, nan, 1u);
+          note_abs(abs_T(f.v[k]), mf, nan, 2u);
+        }
       }
+      st_pack_user(a.y, i, a.n, aly, acc);
+      st_pack_user(a.F, i, a.n, alf, f);
     }
-    st_pack_user(a.y, i, a.n, aly, y);
-    st_pack_user(a.F, i, a.n, alf, f);
+  } else {
+    for (int64_t i = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * N; i < a.n; i += (int64_t)gridDim.x * BLOCK * N) {
+      const Pack<T> xi = ld_pack_user(a.x, i, a.n, alx);
+      Pack<T> acc = ld_pack_user(a.y, i, a.n, aly);
+      Pack<T> f = ld_pack_user(a.F, i, a.n, alf);
+      Pack<T> u[PHIV_TAYLOR_PMAX];
+      if (pa.mask) phiv_load<T>(pa, i, u);
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        T v, y;
+        taylor_product(acc.v[k], a.mu, xi.v[k], a.c, v, y);
+        if (pa.mask) phiv_add<T>(pa, u, k, y);
+        acc.v[k] = y;
+        f.v[k] = add_as_written(f.v[k], y);
+        if (i + k < a.n) {
+          note_abs(abs_T(y), mv, nan, 1u);
+          note_abs(abs_T(f.v[k]), mf, nan, 2u);
+        }
+      }
+      st_pack_user(a.y, i, a.n, aly, acc);
+      st_pack_user(a.F, i, a.n, alf, f);
+    }
   }
   if (taylor_arrive(a.st, mv, mf, nan) && threadIdx.x == 0) taylor_term_test(a.st, a.tol, a.j, a.m, pa.tail);
 }
@@ -247,12 +247,22 @@ __global__ __launch_bounds__(BLOCK) void k_phiv_plan(int mode, int kind, int64_t
 
 namespace {
 
-inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-double f64_of(unsigned long long u) { double d; std::memcpy(&d, &u, 8); return d; }
-
 struct PhivPlan {
   double nu = 1.0, U = 0.0;
 };
+
+// The complex products of the host side, spelled out (see taylor_stage_factor, taylor_state.h: written as a * b the host compiler
+// fuses one product of each component and picks which one from the code around).  A product that only feeds an fma leaves nothing
+// to contract.  phiv_cmul(a, z): what multiplies the tail zeta.  phiv_stage_factor: exp(mu h); its real part fuses the OTHER
+// product, as this file's factor always has -- it is not taylor_stage_factor's, and one-column calls do not come here.
+inline std::complex<double> phiv_cmul(std::complex<double> a, std::complex<double> z) {
+  const double pr = a.imag() * z.imag(), pi = a.real() * z.imag();
+  return std::complex<double>(std::fma(a.real(), z.real(), -pr), std::fma(a.imag(), z.real(), pi));
+}
+inline std::complex<double> phiv_stage_factor(std::complex<double> mu, std::complex<double> h) {
+  const double pr = mu.real() * h.real(), pi = mu.real() * h.imag();
+  return std::exp(std::complex<double>(std::fma(-mu.imag(), h.imag(), pr), std::fma(mu.imag(), h.real(), pi)));
+}
 
 // mu, alpha, nu, U (two launches and one blocking read; a matrix-free operator: one launch) and (m*, s).  Bd: the block in the
 // operator's ordering, column-major.  `head`: taylor_head_bytes() of device memory; its state is ready for the first closing launch.
@@ -300,81 +310,51 @@ void phiv_plan_T(Ctx *c, Op &op, std::complex<double> t, const T *Bd, int64_t ld
 template <class T>
 void phiv_run_T(Ctx *c, Op &op, std::complex<double> t, const T *Bd, int64_t ldb, int p, const PhivPlan &pp, void *state, void *v0, void *v1,
                 void *Fv, TaylorCall &tc) {
-  hipStream_t s = c->stream;
-  const int64_t n = op.n;
-  dev::TaylorState *st = reinterpret_cast<dev::TaylorState *>(state);
   T *V[2] = {reinterpret_cast<T *>(v0), reinterpret_cast<T *>(v1)};
-  T *F = reinterpret_cast<T *>(Fv);
   const std::complex<double> mu(tc.mu_re, tc.mu_im);
   const int m = tc.m;
   const int64_t ns = tc.s;
   const std::complex<double> h = t / (double)ns;
-
-  const bool fused = op.kind == OP_CSR && op.sell_ok && op.ovf_nseg == 0 && !op.cbf;
-  tc.path = fused ? 1 : 2;
+  const TaylorLaunch<T> L(c, op, tc, reinterpret_cast<T *>(Fv), reinterpret_cast<dev::TaylorState *>(state));
   dev::PhivTermArgs<T> pa{};
   dev::TaylorTermArgs<T> &a = pa.t;
-  if (fused) {
-    a.A = dev::SellView<T>{op.sell_off.as<int64_t>(), op.sell_col.as<int32_t>(), op.sell_val.as<T>(), op.nslices};
-    if (op.gndiag > 0 && c->opt.dia) {
-      a.dia_val = op.gdia_ptr<T>(); a.dia_ld = op.gdia_ld; a.ndiag = op.gndiag; a.dia_off = op.gdia_off.as<int32_t>();
-    }
-  }
-  a.F = F; a.n = n; a.mu = taylor_scalar<T>(mu); a.tol = tc.tol; a.m = m; a.st = st;
+  a = L.args();
   pa.B = Bd; pa.ldb = ldb;
-  constexpr int SH = 64 * dev::Pack<T>::N;
-  const int g_fused = dev::taylor_grid((n + SH - 1) / SH, dev::BLOCK / 64);
-  const int g_elem = dev::taylor_grid(n, dev::BLOCK * dev::Pack<T>::N);
-  const std::complex<double> eta = std::exp(mu * h);
-  const bool scale = !(eta.real() == 1.0 && eta.imag() == 0.0);
+  const std::complex<double> eta = phiv_stage_factor(mu, h);
 
   // the tail at the start of a stage: zeta[i - 1] = tau^(p - i) / (p - i)!, i = 1 .. p
   std::complex<double> zeta[PHIV_TAYLOR_PMAX], next[PHIV_TAYLOR_PMAX];
   auto stage_tail = [&](int64_t stage) {
     const std::complex<double> tau = (double)stage * h;
     if (p > 0) zeta[p - 1] = 1.0;
-    for (int i = p - 1; i >= 1; --i) zeta[i - 1] = zeta[i] * tau / (double)(p - i);
+    for (int i = p - 1; i >= 1; --i) zeta[i - 1] = phiv_cmul(tau, zeta[i]) / (double)(p - i);
   };
   auto tail_norm = [&] {
     double z = 0.0;
     for (int i = 0; i < p; ++i) z = std::max(z, std::abs(zeta[i]));
     return z * pp.U;
   };
-  auto close = [&](const T *src, T *v, int sc, int64_t stage) {      // (zeta: the tail of the stage that follows)
-    ProfScope ps(c, EXPV_MI_K_LINCOMB);
-    hipLaunchKernelGGL(dev::k_taylor_close<T>, dim3(g_elem), dim3(dev::BLOCK), 0, s, src, F, v, n, taylor_scalar<T>(eta), sc,
-                       (int)std::min<int64_t>(stage, 2147483646), (int)(stage + 1 < ns), tail_norm(), st);
-  };
   int q = 0;
   stage_tail(0);
-  close(Bd, V[0], 0, -1);
+  L.close(Bd, V[0], eta, -1, tail_norm());      // (zeta: the tail of the stage that follows)
   for (int64_t stage = 0; stage < ns; ++stage) {
     for (int j = 1; j <= m; ++j) {
       const std::complex<double> cj = h / (double)j;
       pa.mask = 0u;
       for (int k = 1; k <= p; ++k) {      // u_k takes g_j[p + 1 - k] = c_j zeta_{j-1}[p + 1 - k]
-        pa.g[k - 1] = taylor_scalar<T>(cj * zeta[p - k]);
+        pa.g[k - 1] = taylor_scalar<T>(phiv_cmul(cj, zeta[p - k]));
         if (!(ST<T>::abs2(pa.g[k - 1]) == 0)) pa.mask |= 1u << (k - 1);
       }
-      for (int i = 0; i < p; ++i) next[i] = cj * ((i + 1 < p ? zeta[i + 1] : std::complex<double>(0.0, 0.0)) - mu * zeta[i]);
+      for (int i = 0; i < p; ++i) next[i] = phiv_cmul(cj, (i + 1 < p ? zeta[i + 1] : std::complex<double>(0.0, 0.0)) - phiv_cmul(mu, zeta[i]));
       for (int i = 0; i < p; ++i) zeta[i] = next[i];
       pa.tail = tail_norm();
       a.x = V[q]; a.y = V[1 - q]; a.j = j;
       a.c = taylor_scalar<T>(cj);
-      if (fused) {
-        ++c->cnt_opapply;
-        ProfScope ps(c, EXPV_MI_K_MATVEC);
-        hipLaunchKernelGGL(dev::k_phiv_term_fused<T>, dim3(g_fused), dim3(dev::BLOCK), 0, s, pa);
-      } else {
-        op_apply_dev(op, a.x, a.y, nullptr, 0);
-        ProfScope ps(c, EXPV_MI_K_LINCOMB);
-        hipLaunchKernelGGL(dev::k_phiv_term_update<T>, dim3(g_elem), dim3(dev::BLOCK), 0, s, pa);
-      }
-      ++tc.launches;
+      L.term(pa, a.x, a.y, [](auto fused) { return dev::k_phiv_term<T, decltype(fused)::value>; });
       q ^= 1;
     }
     stage_tail(stage + 1);
-    close(F, V[q], scale ? 1 : 0, stage);
+    L.close(L.F, V[q], eta, stage, tail_norm());
   }
   HIPCHECK(hipGetLastError());
 }

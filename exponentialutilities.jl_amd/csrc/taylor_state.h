@@ -1,10 +1,12 @@
-// taylor_state.h -- the device-resident stage state of the truncated-Taylor exp(tA)b and the helpers its kernels share
-// (expv_taylor.hip: one vector; expv_taylor_block.hip: a block of columns; phiv_taylor.hip: the series on the augmented matrix, which
-// also launches the arrival / stopping-test / closing code below).  gfx950 only.
+// taylor_state.h -- what every truncated-Taylor entry shares below the row sweep: the device-resident stage state, the arrival of
+// a launch's workgroups, F's stopping test, the closing kernel, and THE ELEMENT STEP -- the one definition of the roundings of a
+// term, used by the single, phiv, grid and block kernels, which is why their results agree bit for bit.  (The row sweep of the
+// single-column families and the host-side launch setup: taylor_term.h.)  gfx950 only.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <complex>
+#include <cstring>
 
 #include "kernel_common.h"
 
@@ -67,7 +69,70 @@ __device__ __forceinline__ void note_abs(double a, double &m, unsigned &nan, uns
   else m = fmax(m, a);
 }
 
-// ---- one launch of the series: arrival, the stopping test, the closing kernel (expv_taylor.hip, phiv_taylor.hip) ----
+__device__ __forceinline__ double taylor_qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// ---- the element step: the roundings of one term, by definition ----
+// Every operation below is either an explicit fused multiply-add or stands under `fp contract(off)`: the compiler has nothing to
+// fuse or to leave unfused, so the same operands give the same bits in every kernel that calls these.
+//   c a        real: the rounded product.  complex: re = fma(c.re, a.re, -(c.im a.im));  im = fma(c.re, a.im, c.im a.re) in
+//              ComplexF64, fma(c.im, a.re, c.re a.im) in ComplexF32 (the pairing of the packed fp32 multiply-add).
+//   F + c a    real: ONE fused multiply-add fma(c, a, F).  complex: the plain sum of F and the rounded c a, per component.
+__device__ __forceinline__ double mul_as_single(double c, double a) {
+#pragma clang fp contract(off)
+  return c * a;
+}
+__device__ __forceinline__ float mul_as_single(float c, float a) {
+#pragma clang fp contract(off)
+  return c * a;
+}
+__device__ __forceinline__ cplx mul_as_single(cplx c, cplx a) {
+#pragma clang fp contract(off)
+  const double pr = c.im * a.im, pi = c.im * a.re;
+  return make_cplx(fma(c.re, a.re, -pr), fma(c.re, a.im, pi));
+}
+__device__ __forceinline__ cplx32 mul_as_single(cplx32 c, cplx32 a) {
+#pragma clang fp contract(off)
+  const float pr = c.im * a.im, pi = c.re * a.im;
+  return make_cplx32(fmaf(c.re, a.re, -pr), fmaf(c.im, a.re, pi));
+}
+// a + b as written, per component: never fused with the product that made b
+template <class T>
+__device__ __forceinline__ T add_as_written(T a, T b) {
+#pragma clang fp contract(off)
+  if constexpr (ST<T>::is_complex) {
+    a.re = a.re + b.re;
+    a.im = a.im + b.im;
+    return a;
+  } else {
+    return a + b;
+  }
+}
+// F + c a, given y = mul_as_single(c, a)
+template <class T>
+__device__ __forceinline__ T term_sum(T f, T c, T a, T y) {
+  if constexpr (ST<T>::is_complex) {
+    return add_as_written(f, y);
+  } else {
+    ST<T>::fma_(f, c, a);
+    return f;
+  }
+}
+// One element of a term in two halves: v = acc - mu x_i (acc = (A x)_i) and cv = c v, the next v_i ...
+template <class T>
+__device__ __forceinline__ void taylor_product(T acc, T mu, T xi, T c, T &v, T &cv) {
+  v = acc;
+  ST<T>::nfma(v, mu, xi);
+  cv = mul_as_single(c, v);
+}
+// ... and fn = F_i + c v.  (A family that adds to cv before it enters F takes the first half and owns the sum: phiv_taylor.hip.)
+template <class T>
+__device__ __forceinline__ void taylor_step(T acc, T mu, T xi, T c, T f, T &cv, T &fn) {
+  T v;
+  taylor_product(acc, mu, xi, c, v, cv);
+  fn = term_sum<T>(f, c, v, cv);
+}
+
+// ---- one launch of the series: arrival, the stopping test, the closing kernel ----
 
 // Every thread of every workgroup of a launch: this workgroup's maxima into the state, then one ticket.  True in the workgroup that
 // arrives last, whose lane 0 then owns the state (everything the others added was performed before their tickets).
@@ -99,40 +164,37 @@ __device__ __forceinline__ void taylor_rearm(TaylorState *st) {
   ts_store(&st->nanflags, 0ull);
   ts_store(&st->ticket, 0ull);
 }
-// lane 0 of the last workgroup of a term launch: the test of the reference's loop (:153-155).  tail: a floor under |v|_inf (the part
-// of the term that lives outside the n rows, phiv_taylor.hip; 0 for exp(tA)b, where max(x, 0) = x for the non-negative maximum)
-__device__ __forceinline__ void taylor_term_test(TaylorState *st, double tol, int j, int m, double tail) {
-  const unsigned long long nan = ts_load(&st->nanflags);
-  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-  const double c2 = (nan & 1ull) ? qnan : fmax(ts_loadf(&st->maxv), tail);
-  const double fn = (nan & 2ull) ? qnan : ts_loadf(&st->maxf);
-  const double c1 = ts_loadf(&st->c1);
-  ts_store(&st->apps, ts_load(&st->apps) + 1ull);
+// lane 0 of the last workgroup of a term launch.  `nan` is the state's nanflags word, read ONCE per test: every access below is a
+// round trip to device memory on the critical path of the launch, so the loads of a test are issued together, ahead of its stores.
+__device__ __forceinline__ double taylor_vmax(const TaylorState *st, unsigned long long nan) {      // |v_j|_inf (NaN when v held one)
+  return (nan & 1ull) ? taylor_qnan() : ts_loadf(&st->maxv);
+}
+__device__ __forceinline__ double taylor_fnorm(const TaylorState *st, unsigned long long nan) {     // |F|_inf (NaN when F held one)
+  return (nan & 2ull) ? taylor_qnan() : ts_loadf(&st->maxf);
+}
+// F's test of the reference's loop (:153-155): c1 = |v_{j-1}|_inf, c2 = |v_j|_inf, fn = |F|_inf
+__device__ __forceinline__ void taylor_f_test(TaylorState *st, double c1, double c2, double fn, double tol, int j, int m) {
   if (c1 + c2 <= tol * fn) {
     ts_store(&st->stopped, 1ull);
     if (j < m) ts_store(&st->early, ts_load(&st->early) + 1ull);
   } else {
     ts_storef(&st->c1, c2);
   }
+}
+// The whole test of a single-column term.  tail: a floor under |v|_inf (the part of the term that lives outside the n rows,
+// phiv_taylor.hip; 0 for exp(tA)b, where max(x, 0) = x for the non-negative maximum)
+__device__ __forceinline__ void taylor_term_test(TaylorState *st, double tol, int j, int m, double tail) {
+  const unsigned long long nan = ts_load(&st->nanflags);
+  const double c2 = (nan & 1ull) ? taylor_qnan() : fmax(ts_loadf(&st->maxv), tail);
+  const double fn = taylor_fnorm(st, nan);
+  const double c1 = ts_loadf(&st->c1);
+  ts_store(&st->apps, ts_load(&st->apps) + 1ull);
+  taylor_f_test(st, c1, c2, fn, tol, j, m);
   taylor_rearm(st);
 }
 __device__ __forceinline__ bool taylor_skip(const TaylorState *st) {
   return (ts_load(&st->stopped) | ts_load(&st->ended)) != 0ull;
 }
-
-template <class T>
-struct TaylorTermArgs {
-  SellView<T> A;                                  // SELL slots (ndiag == 0) ...
-  const T *dia_val; int64_t dia_ld; int ndiag; const int32_t *dia_off;      // ... or the general diagonal form
-  const T *x;                                     // v of the previous term
-  T *y;                                           // fused: out.  update: in (A x as mul! left it) and out
-  T *F;
-  int64_t n;
-  T c, mu;                                        // (t / s) / j and tr(A) / n
-  double tol;
-  int j, m;
-  TaylorState *st;
-};
 
 // Closes a stage (:157-159): F = eta src (scale == 0: F = src as it is), v = F, c1 = |F|_inf, the finite test, and the state of the
 // next stage.  The first launch of a call is this kernel with src = b, scale = 0 and stage = -1 (no finite test: the reference
@@ -149,14 +211,14 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_close(const T *src, T *F, T *v
     Pack<T> f = ld_pack_user(src, i, n, als);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      if (scale) f.v[k] = ST<T>::mul(eta, f.v[k]);
+      if (scale) f.v[k] = mul_as_single(eta, f.v[k]);
       if (i + k < n) note_abs(abs_T(f.v[k]), mf, nan, 2u);
     }
     if (scale || src != F) st_pack_user(F, i, n, alf, f);
     st_pack_user(v, i, n, alv, f);
   }
   if (taylor_arrive(st, 0.0, mf, nan) && threadIdx.x == 0) {
-    const double fn = (ts_load(&st->nanflags) & 2ull) ? __longlong_as_double(0x7ff8000000000000ll) : ts_loadf(&st->maxf);
+    const double fn = (ts_load(&st->nanflags) & 2ull) ? taylor_qnan() : ts_loadf(&st->maxf);
     ts_storef(&st->c1, fn != fn ? fn : fmax(fn, tail));
     ts_storef(&st->fnorm, fn);
     const bool finite = fn < __longlong_as_double(0x7ff0000000000000ll);
@@ -172,42 +234,16 @@ __global__ __launch_bounds__(BLOCK) void k_taylor_close(const T *src, T *F, T *v
   }
 }
 
-// The roundings of `mul(c, a)` and `F + mul(c, a)` as k_taylor_term_fused, k_taylor_term_update and k_taylor_close are compiled.
-// ST<T>::mul and ST<T>::add are written as products and sums, and the compiler contracts them where it meets them:
-//   real types      y = c a rounded, F + c a ONE fused multiply-add;
-//   complex types   re = fma(c.re, a.re, -(c.im a.im)) in both; im = fma(c.re, a.im, c.im a.re) in ComplexF64 but
-//                   fma(c.im, a.re, c.re a.im) in ComplexF32 (a packed instruction pairs the operands the other way); F + y plain sums.
-// Which product it fuses depends on the code around (the masking here hides the real product from the sum, and the complex close
-// came out the other way round), so the block and grid kernels spell the single kernels' operations out as explicit fused multiply-adds: a product
-// that only feeds an fma, and a sum of an fma, leave nothing to contract.  Nothing pins the compiler's choice THERE:
-// tests/test_gpu_expv_taylor_block.py and tests/test_gpu_expv_taylor_grid.py hold them to the same bits, for every element type.
-__device__ __forceinline__ double mul_as_single(double c, double a) { return c * a; }
-__device__ __forceinline__ float mul_as_single(float c, float a) { return c * a; }
-__device__ __forceinline__ cplx mul_as_single(cplx c, cplx a) {
-  const double pr = c.im * a.im, pi = c.im * a.re;
-  return make_cplx(fma(c.re, a.re, -pr), fma(c.re, a.im, pi));
-}
-__device__ __forceinline__ cplx32 mul_as_single(cplx32 c, cplx32 a) {
-  const float pr = c.im * a.im, pi = c.re * a.im;
-  return make_cplx32(fmaf(c.re, a.re, -pr), fmaf(c.im, a.re, pi));
-}
-// F + c a, given y = mul_as_single(c, a)
-template <class T>
-__device__ __forceinline__ T term_sum(T f, T c, T a, T y) {
-  if constexpr (ST<T>::is_complex) {
-    return ST<T>::add(f, y);
-  } else {
-    ST<T>::fma_(f, c, a);
-    return f;
-  }
-}
-
-static int taylor_grid(int64_t n, int rows_per_block) {
-  int64_t g = (n + rows_per_block - 1) / rows_per_block;
+// workgroups for `items` rows (or slices) at `per_block` each
+static int taylor_grid(int64_t items, int per_block) {
+  int64_t g = (items + per_block - 1) / per_block;
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, MAX_GRID));
 }
 
 }  // namespace dev
+
+static inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
+static inline double f64_of(unsigned long long u) { double d; std::memcpy(&d, &u, 8); return d; }
 
 // The stage factor exp(mu t / s) in double.  The complex product is spelled out: written as mu * t the host compiler fuses one
 // product of each component into a multiply-add and picks WHICH ONE from the code around, so that two callers disagree in the last
