@@ -936,6 +936,19 @@ class MIOperator:
                 "column_indices_stored": int(out[6]), "ring_entries_per_tile": int(out[7])}
 
     @property
+    def elide_info(self):
+        """Constant tiles of a banded Float64 operator (expv_mi_op_elide_info; context option "elide"): ``tiles`` of 512 stored rows,
+        ``diagonals``, ``constant_pairs`` -- the (tile, diagonal) pairs on which the stored diagonal holds one bit pattern, which the
+        single-pass step reads as one entry instead of streaming --, ``wholly_constant`` -- every diagonal constant on all its rows --
+        and ``mask``: one uint8 per tile, bit d = diagonal d.  All zero / empty for operators without that stored form."""
+        out = (C.c_int64 * 4)()
+        _check(L.load().expv_mi_op_elide_info(self._h, out, None, 0))
+        mask = np.zeros(int(out[0]), dtype=np.uint8)
+        if mask.size:
+            _check(L.load().expv_mi_op_elide_info(self._h, out, mask.ctypes.data, mask.size))
+        return {"tiles": int(out[0]), "diagonals": int(out[1]), "constant_pairs": int(out[2]), "wholly_constant": bool(out[3]), "mask": mask}
+
+    @property
     def ingest_info(self):
         """How a sparse operator came to be (expv_mi_op_ingest_info): ``from_device`` -- created from arrays on the device --,
         the bytes of pattern and of values that were brought to the host for it (values: 0 unless a row is unsorted or holds a

@@ -608,6 +608,11 @@ static void op_fill_forms(Op &op, bool creation, bool check_herm, unsigned long 
     a.sell_cut = op.sell_cut;
   }
   if (op.ndiag > 0) { a.dia = op.dia_val.as<T>(); a.dia_ld = op.dia_ld; a.nd = op.ndiag; a.dia_off = op.gdia_off.as<int32_t>(); }
+  if (op.ndiag > 0 && op.ndiag <= 8 && std::is_same<T, double>::value) {      // (the kernel writes every byte: no memset)
+    op.dia_tiles = (op.dia_ld + 511) / 512;
+    if (op.dia_tile_mask.bytes < (size_t)op.dia_tiles) op.dia_tile_mask.alloc((size_t)op.dia_tiles + 16);
+    a.dia_tile_mask = op.dia_tile_mask.as<unsigned char>();
+  }
   else if (op.gndiag > 0 && !op.gdia_alias) { a.dia = op.gdia_val.as<T>(); a.dia_ld = op.gdia_ld; a.nd = op.gndiag; a.dia_off = op.gdia_off.as<int32_t>(); }
   a.check_herm = check_herm ? 1 : 0;
   a.out = op.upd_out.as<unsigned long long>();
@@ -623,6 +628,7 @@ static void op_fill_forms(Op &op, bool creation, bool check_herm, unsigned long 
       std::memcpy(&op.dia_const[d], &out[16 + d], sizeof(double));
     }
     op.dia_is_const = cst;
+    op.dia_tiles_const = a.dia_tile_mask ? (int64_t)out[24] : 0;
   }
 }
 
@@ -2273,6 +2279,25 @@ int expv_mi_op_patch_info(expv_mi_op_t op, int64_t out[8]) {
   out[6] = op->ring_col_unique;
   out[7] = op->ring_pad;
   return EXPV_MI_OK;
+}
+
+int expv_mi_op_elide_info(expv_mi_op_t op, int64_t out[4], unsigned char *mask, int64_t mask_len) {
+  if (!op || !out) return EXPV_MI_ARGUMENT_ERROR;
+  return guarded(op->ctx, [&] {
+    op->ctx->use();
+    const bool has = op->dia_tile_mask.p != nullptr && op->ndiag > 0;
+    out[0] = has ? op->dia_tiles : 0;
+    out[1] = has ? op->ndiag : 0;
+    out[2] = has ? op->dia_tiles_const : 0;
+    out[3] = op->dia_is_const ? 1 : 0;
+    if (mask && mask_len > 0) {
+      std::memset(mask, 0, (size_t)mask_len);
+      if (has) {
+        HIPCHECK(hipMemcpyAsync(mask, op->dia_tile_mask.p, (size_t)std::min<int64_t>(mask_len, op->dia_tiles), hipMemcpyDeviceToHost, op->ctx->stream));
+        HIPCHECK(hipStreamSynchronize(op->ctx->stream));
+      }
+    }
+  });
 }
 
 int expv_mi_op_update_values(expv_mi_op_t op, const void *vals, int loc) {

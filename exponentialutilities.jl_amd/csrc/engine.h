@@ -87,6 +87,8 @@ struct Options {
   int pipeline_serial = 0; // single-pass step: one launch after the other even if overlap is on (EXPV_MI_PIPE_SERIAL=1 -> 1)
   int spin_limit = 400000; // polls (~1 us each) before a waiting kernel gives up               (EXPV_MI_PIPE_SPIN_LIMIT)
   int batch_rounds = 2;    // batched single-pass step: resident rounds of fat workgroups       (EXPV_MI_BATCH_ROUNDS)
+  int elide = 1;           // fp64 banded operators: a diagonal that holds one value on a whole 512-row tile is read as one entry there, not
+                           // streamed (per tile and diagonal, found at creation / values update; bitwise neutral)      (EXPV_MI_ELIDE=0 -> 0)
   int stencil = 0;         // constant-coefficient banded operators: pass the diagonals as scalars, do not stream them (EXPV_MI_STENCIL=1 -> 1)
   int nontemporal = -1;    // non-temporal loads in the single-pass step: -1 by footprint, 0 never, 1 always  (EXPV_MI_NONTEMPORAL=0|1)
   int recycle = 1;         // a destroyed KrylovSubspace's storage is kept (one per context) for the next create of the same shape (EXPV_MI_NO_RECYCLE=1 -> 0)
@@ -304,6 +306,11 @@ struct Op {
   int ndiag = 0;
   bool dia_is_const = false;      // every stored diagonal of the DIA form holds one value (constant-coefficient stencil)
   double dia_const[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // per tile of 512 stored rows and diagonal: the tile holds ONE bit pattern, zero fill included (kernels.hip: k_op_dia_const) -- the
+  // single-pass step then reads one entry of the tile instead of streaming it (pipe.hip; context option "elide").  One byte per
+  // tile, bit d = diagonal d; recomputed with the forms at creation and at every values update
+  DevBuf dia_tile_mask;
+  int64_t dia_tiles = 0, dia_tiles_const = 0;      // tiles of the DIA form; (tile, diagonal) pairs whose bit is set
   int64_t dia_ld = 0;
   int dia_off[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // general DIA form (fp64, any offsets, <= GDIA_MAX diagonals, <= 30 % zero fill): structured-grid stencils; read by

@@ -382,6 +382,7 @@ Options Options::from_env() {
   if (flag("EXPV_MI_NO_RECYCLE")) o.recycle = 0;
   if (flag("EXPV_MI_EE_STEPWISE")) o.ee_blocked = 0;
   if (flag("EXPV_MI_STENCIL")) o.stencil = 1;
+  if (const char *e = std::getenv("EXPV_MI_ELIDE")) o.elide = std::atoi(e) ? 1 : 0;
   if (const char *e = std::getenv("EXPV_MI_NONTEMPORAL")) o.nontemporal = std::atoi(e) ? 1 : 0;
   if (flag("EXPV_MI_PIPE_SERIAL")) o.pipeline_serial = 1;
   if (const char *v = std::getenv("EXPV_MI_PIPE_SPIN_LIMIT")) o.spin_limit = std::atoi(v);
@@ -402,6 +403,7 @@ int *Options::find(const char *name) {
   if (n == "recycle") return &recycle;
   if (n == "ee_blocked") return &ee_blocked;
   if (n == "stencil") return &stencil;
+  if (n == "elide") return &elide;
   if (n == "nontemporal") return &nontemporal;
   if (n == "pipeline_serial") return &pipeline_serial;
   if (n == "reorder") return &reorder;
@@ -940,6 +942,8 @@ struct ArnoldiCall {
         if (!ST<T>::is_complex && c->opt.stencil && op.dia_is_const && !isaug) {   // constant-coefficient stencil: scalars instead of streams
           pa.dia_const = 1;
           for (int d = 0; d < op.ndiag; ++d) pa.dia_c[d] = op.dia_const[d];
+        } else if (std::is_same<T, double>::value && c->opt.elide && op.dia_tiles_const > 0 && !isaug) {
+          pa.dia_mask = op.dia_tile_mask.as<unsigned char>();      // tiles on which a diagonal holds one value: one entry read, not 4 KB
         }
       }
       pa.w = use_ring ? 0 : (int)op.bandwidth;

@@ -78,7 +78,8 @@ struct OpUpdateArgs {
   T *dia; int64_t dia_ld; const int32_t *dia_off; int nd;   // [nd][dia_ld] diagonal form with device offsets (nullptr: none)
   int check_herm;               // rows have strictly ascending columns: test A == A^H (explicit zeros ignored) on the device
   unsigned long long *out;      // [0] bits of max_r sum_k |a_rk|, [1] != 0: not Hermitian, [2 + d] != 0: diagonal d not constant,
-                                // [16 + d] bits of the first entry of diagonal d
+                                // [16 + d] bits of the first entry of diagonal d, [24] set bits of dia_tile_mask
+  unsigned char *dia_tile_mask; // fp64 banded form: one byte per tile of 512 stored rows, bit d = diagonal d holds one bit pattern on the tile (nullptr: not wanted)
 };
 template <class T> void op_scatter_values(hipStream_t s, T *dst, const T *src, const int32_t *pos, int64_t nnz);
 // ---- a caller's CSR / CSC index arrays on the device, checked and normalised there (op_ingest.hip; capi.hip: create_sparse_device) ----
@@ -359,6 +360,8 @@ struct PipeArgsT {
   int spin_limit;              // polls before a waiting kernel gives up (status 99 -> the host redoes the call serially)
   int dia_const;               // DIA form, fp64: the diagonals are constants (dia_c), nothing is read from dia_val
   double dia_c[PIPE_DIA_MAX];
+  const unsigned char *dia_mask;   // DIA halo form, fp64: per tile of 512 rows, bit d = diagonal d holds ONE bit pattern on the tile's stored rows:
+                               // the lanes read its first entry instead of their own (same values, one line of traffic); null: stream everything
   int nt_mode;                 // non-temporal loads for the streamed operands: 0 by footprint, 1 never, 2 always (pipe.hip)
   // continuation (arnoldi!(...; init = j), arnoldi.jl:350,368): the first pass of the call takes the stored, normalised
   // v_j (yprev = its column, inv = 1, zero coefficients): its norm is 1 by construction, H[j, j-1] is already known

@@ -1222,29 +1222,54 @@ __global__ __launch_bounds__(BLOCK) void k_op_update_forms(const OpUpdateArgs<T>
   if ((threadIdx.x & 63) == 0 && m > 0.0) atomicMax(a.out + 0, (unsigned long long)__double_as_longlong(m));
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(a.out + 1, 1ull);
 }
-// constant diagonals (fp64 banded form): block d compares the entries diagonal d can have with its first one
+// constant diagonals (fp64 banded form), ONE pass over the stored diagonals.  A wave owns a tile of 512 stored rows (the tile of the
+// single-pass step, pipe.hip) and walks its diagonals: diagonal d of the tile is "constant" when all 512 STORED entries carry one bit
+// pattern -- the zero fill outside the matrix and up to dia_ld counts, +0.0 and -0.0 differ, a NaN anywhere clears the bit -- so
+// that the splat of the tile's first stored entry IS the tile (mask[tile] bit d; out[24] counts the set bits).  On the way the entries
+// diagonal d can have (rows rlo .. rhi-1) are compared with its first one: the whole-operator answer (out[2 + d], out[16 + d]).
 template <class T>
-__global__ __launch_bounds__(BLOCK) void k_op_dia_const(const T *__restrict__ dia, int64_t ld, const int32_t *__restrict__ off,
-                                                        int64_t n, unsigned long long *out) {
-  const int d = blockIdx.x;
-  const int64_t o = off[d], rlo = o < 0 ? -o : 0, rhi = o > 0 ? n - o : n;
-  if (rhi <= rlo) { if (threadIdx.x == 0) out[2 + d] = 1ull; return; }
-  const T c0 = dia[(int64_t)d * ld + rlo];
-  bool diff = false;
-  for (int64_t r = rlo + (int64_t)blockIdx.y * BLOCK + threadIdx.x; r < rhi; r += (int64_t)gridDim.y * BLOCK) {   // (one block per diagonal took 1.2 ms at n = 1e6)
-    const T v = dia[(int64_t)d * ld + r];
-    diff = diff || upd_bits(v) != upd_bits(c0) || !upd_eq_conj(v, v) || !upd_eq_conj(c0, c0);
+__global__ __launch_bounds__(BLOCK) void k_op_dia_const(const T *__restrict__ dia, int64_t ld, const int32_t *__restrict__ off, int nd,
+                                                        int64_t n, unsigned long long *out, unsigned char *__restrict__ mask) {
+  constexpr int TILE = 512, PER = TILE / 64;
+  const int lane = threadIdx.x & 63;
+  const int64_t tile = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+  if (tile * TILE >= ld) return;      // (whole waves)
+  const int64_t r0 = tile * TILE;
+  unsigned bits = 0;
+  for (int d = 0; d < nd; ++d) {
+    const int64_t o = off[d], rlo = o < 0 ? -o : 0, rhi = o > 0 ? n - o : n;
+    const T *row = dia + (int64_t)d * ld;
+    if (rhi <= rlo) { if (tile == 0 && lane == 0) out[2 + d] = 1ull; continue; }
+    const T c0 = row[rlo], t0 = row[r0];
+    bool diff = !upd_eq_conj(c0, c0), tdiff = !upd_eq_conj(t0, t0);      // (NaN: never constant)
+    T v[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) v[q] = row[r0 + q * 64 + lane];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int64_t r = r0 + q * 64 + lane;
+      const bool nan = !upd_eq_conj(v[q], v[q]);
+      tdiff = tdiff || nan || upd_bits(v[q]) != upd_bits(t0);
+      if (r >= rlo && r < rhi) diff = diff || nan || upd_bits(v[q]) != upd_bits(c0);
+    }
+    if (__any(diff) && lane == 0) atomicOr(out + 2 + d, 1ull);
+    if (!__any(tdiff)) bits |= 1u << d;
+    if (tile == 0 && lane == 0) out[16 + d] = upd_bits(c0);
   }
-  if (__any(diff) && (threadIdx.x & 63) == 0) atomicOr(out + 2 + d, 1ull);
-  if (threadIdx.x == 0) out[16 + d] = upd_bits(c0);
+  if (lane == 0) {
+    if (mask) mask[tile] = (unsigned char)bits;
+    if (mask && bits) atomicAdd(out + 24, (unsigned long long)__popc(bits));
+  }
 }
 template <class T>
 void op_update_forms(hipStream_t s, const OpUpdateArgs<T> &a) {
   if (a.n <= 0) return;
   hipLaunchKernelGGL(k_op_update_forms<T>, dim3((unsigned)((a.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, a);
-  if (a.dia && a.nd > 0 && a.nd <= 8 && std::is_same<T, double>::value)      // (constant-coefficient option of the fp64 banded step)
-    hipLaunchKernelGGL(k_op_dia_const<T>, dim3(a.nd, (unsigned)std::max<int64_t>(1, std::min<int64_t>(256, a.n / (4 * BLOCK)))), dim3(BLOCK), 0, s, a.dia,
-                       a.dia_ld, a.dia_off, a.n, a.out);
+  if (a.dia && a.nd > 0 && a.nd <= 8 && std::is_same<T, double>::value) {      // (constant-coefficient forms of the fp64 banded step)
+    const int64_t tiles = (a.dia_ld + 511) / 512;
+    hipLaunchKernelGGL(k_op_dia_const<T>, dim3((unsigned)((tiles + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, s, a.dia, a.dia_ld, a.dia_off, a.nd,
+                       a.n, a.out, a.dia_tile_mask);
+  }
 }
 struct ulonglong2_u { unsigned long long a, b; };      // a 16-byte element moved as two 8-byte words (8-byte aligned pointers)
 template <class W>

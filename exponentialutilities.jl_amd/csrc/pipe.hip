@@ -258,7 +258,7 @@ template <> struct ColPack<1> { int c[1]; __device__ __forceinline__ void load(c
 // in the overlapped form BEFORE the wait on the previous step's flag; what the previous step wrote (its column of V, its y~) follows
 // into registers together with the first tile's, right behind the flag.
 template <class T, int CH, int PS, bool LIVE, bool DIA, bool WAVE = false, bool AUG = false, bool NT = false, bool RING = false,
-          class SH = PipeSharedT<T>, bool PF = false>
+          class SH = PipeSharedT<T>, bool PF = false, bool EL = false>
 __device__ __forceinline__ int pipe_pass(const PipeArgsT<T> &pa, int tiles_per_block, SH &sh) {
   static_assert(!PF || (DIA && !WAVE && !RING && PS >= 1 && CH == 4 && !NT), "next-tile prefetch: the 4-column variants of the banded DIA halo form");
   // XPF (long windows): a tile's products are reduced part by part (16 values at a time); once BOTH sets of a part are done its
@@ -334,11 +334,13 @@ __device__ __forceinline__ int pipe_pass(const PipeArgsT<T> &pa, int tiles_per_b
         if (tid == q) v = pa.dia_off[q];
       sh.doff[tid] = v;      // (read after the barrier that follows the LDS copy of u_j)
       if constexpr (IS_F64) {
-        double cst = 0.0;
+        if (!EL || pa.dia_const) {      // (EL: otherwise the words hold the tile masks, see ELIDE below)
+          double cst = 0.0;
 #pragma unroll
-        for (int q = 0; q < PIPE_DIA_MAX; ++q)
-          if (tid == q) cst = pa.dia_c[q];
-        sh.dcoef[tid] = cst;
+          for (int q = 0; q < PIPE_DIA_MAX; ++q)
+            if (tid == q) cst = pa.dia_c[q];
+          sh.dcoef[tid] = cst;
+        }
       }
     }
   }
@@ -367,6 +369,32 @@ __device__ __forceinline__ int pipe_pass(const PipeArgsT<T> &pa, int tiles_per_b
       sh.ut[tid] = v;
     }
   };
+  // ELIDE (pa.dia_mask): bit d of a tile's mask byte says that diagonal d holds ONE bit pattern on all 512 stored rows of the tile
+  // (zero fill included; found at creation / values update, kernels.hip k_op_dia_const).  Every lane then reads the tile's FIRST pack
+  // of that diagonal instead of its own: the same values through the same load instruction and the same FMAs, one line of traffic
+  // instead of 4 KB, and the choice is a uniform offset -- no branch, no second code path.  The bytes of ALL the workgroup's tiles are
+  // fetched here, ahead of the prologue's own loads, into the LDS words of the stencil constants (sh.dcoef: the two options exclude
+  // each other): a tile reads its byte from LDS, nothing is carried in registers across the tile loop.  Tiles beyond ELIDE_CAP per
+  // workgroup (n > 16e6 rows) are streamed.
+  // EL: the instantiation the launchers pick when the operator HAS constant tiles; every other operator runs the one without a
+  // trace of this (no loss where it does not apply: the streamed path is the same code as before).
+  static_assert(!EL || (DIA && !WAVE && !RING && !AUG && IS_F64), "tile elision: the fp64 DIA halo form");
+  constexpr bool ELIDE = EL;
+  constexpr int ELIDE_CAP = (int)(sizeof(sh.dcoef));
+  [[maybe_unused]] unsigned char *emask = reinterpret_cast<unsigned char *>(sh.dcoef);
+  bool elide_on = false;                                  // (workgroup-uniform)
+  [[maybe_unused]] unsigned mk = 0, mkn = 0;             // mask byte of the current tile, of the next one (PF)
+  if constexpr (ELIDE) {
+    elide_on = pa.dia_mask != nullptr && !pa.final && !pa.dia_const;
+    if (elide_on) {
+      if (tid < ELIDE_CAP) {      // the tile loop's numbering (halo form: contiguous tiles, or dealt round-robin)
+        const bool rr_ = !PF && pa.xcd_map == 2 && !(!LIVE && gridDim.y > 1);
+        const int64_t t_ = rr_ ? (int64_t)blockIdx.x + (int64_t)tid * gridDim.x : (int64_t)blockIdx.x * tiles_per_block + tid;
+        emask[tid] = (tid < tiles_per_block && t_ < (a.n + TR - 1) / TR) ? pa.dia_mask[t_] : (unsigned char)0;
+      }
+      if (!ready) __syncthreads();      // (ready: the barrier of the prologue below)
+    }
+  }
   if (ready) {
     if (pa.cont) inv = pa.cont_inv;
     else if (!first) inv = a.st->inv;
@@ -432,8 +460,9 @@ __device__ __forceinline__ int pipe_pass(const PipeArgsT<T> &pa, int tiles_per_b
           if (!AUG || in < n_opn) {
 #pragma unroll
             for (int sl = 0; sl < PS; ++sl)
-              if (sl < pa.ndiag)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(dia_val + in + (int64_t)sl * pa.dia_ld),
+              if (sl < pa.ndiag)      // (ELIDE: a diagonal that is constant on the next tile parks the splat -- every lane asks for the tile's first pack)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(dia_val + in + (int64_t)sl * pa.dia_ld -
+                                                                                                  (ELIDE && ((mkn >> sl) & 1u) ? NN * (int64_t)threadIdx.x : 0)),
                                                  (__attribute__((address_space(3))) void *)&us[PARK0 + sl * BLOCK * NN + wbase], 16, 0, 0);
           }
 #pragma unroll
@@ -481,6 +510,14 @@ __device__ __forceinline__ int pipe_pass(const PipeArgsT<T> &pa, int tiles_per_b
     const int64_t r0 = tile * TR, i = r0 + N * (int64_t)tid;
     const bool act = i < nb;   // whole waves: nb is a multiple of the rows a wave owns
     if constexpr (WAVE) WAVE_STAMP(pa.step, tl, 0);
+    if constexpr (ELIDE) {
+      if (elide_on) {
+        mk = tl < ELIDE_CAP ? __builtin_amdgcn_readfirstlane((unsigned)emask[tl]) : 0u;
+        if constexpr (PF) mkn = tl + 1 < ELIDE_CAP ? __builtin_amdgcn_readfirstlane((unsigned)emask[tl + 1]) : 0u;
+      }
+    }
+    // rows back from this lane's pack to the tile's first one where diagonal sl is constant on the tile, 0 where it is streamed
+    [[maybe_unused]] auto elide_back = [&](unsigned m_, int sl) -> int { return ((m_ >> sl) & 1u) ? N * tid : 0; };
     // ---- operator slots of this lane's rows: issued now, consumed after the barrier ------------
     Pack<T> av[PS > 0 ? PS : 1];
     // SELL wave form: the column indices of up to 6 slots are fetched ahead of the flag wait even when the register budget has
@@ -508,7 +545,9 @@ __device__ __forceinline__ int pipe_pass(const PipeArgsT<T> &pa, int tiles_per_b
             if constexpr (IS_F64 && !AUG) {
               if (pa.dia_const) { av[sl].v[0] = av[sl].v[1] = pa.dia_c[sl]; continue; }   // constant-coefficient stencil: nothing to load
             }
-            av[sl] = ld_stream<NT, T>(avp + (int64_t)sl * pa.dia_ld);
+            const T *ap = avp + (int64_t)sl * pa.dia_ld;
+            if constexpr (ELIDE) ap -= elide_back(mk, sl);
+            av[sl] = ld_stream<NT, T>(ap);
           }
       }
     } else if (i < n_op) {      // (rows of the augmentation carry no operator entries)
@@ -1051,7 +1090,11 @@ __device__ __forceinline__ int pipe_pass(const PipeArgsT<T> &pa, int tiles_per_b
           if constexpr (IS_F64 && !AUG) {
             if (pa.dia_const) { v2.v[0] = v2.v[1] = sh.dcoef[sl]; have = true; }
           }
-          if (!have) v2 = ld_stream<NT, T>(avp + (int64_t)sl * pa.dia_ld);
+          if (!have) {
+            const T *ap = avp + (int64_t)sl * pa.dia_ld;
+            if constexpr (ELIDE) ap -= elide_back(mk, sl);
+            v2 = ld_stream<NT, T>(ap);
+          }
           const int o = base + sh.doff[sl];
 #pragma unroll
           for (int e = 0; e < N; ++e) ST<T>::fma_(y.v[e], v2.v[e], us[o + e]);
@@ -1290,11 +1333,11 @@ __device__ __forceinline__ int pipe_pass(const PipeArgsT<T> &pa, int tiles_per_b
   return 1;
 }
 
-template <class T, int CH, int WAVES, int PS, bool DIA, bool AUG = false, bool NT = false, bool PF = false>
+template <class T, int CH, int WAVES, int PS, bool DIA, bool AUG = false, bool NT = false, bool PF = false, bool EL = false>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_pipe(const PipeArgsT<T> pa, int tiles_per_block) {
   using SH = PipeSharedT<T, PF ? (PS + 1) * Pack<T>::N * BLOCK : 0, PF>;      // PF: the park area of the next tile behind us[]
   __shared__ SH sh;
-  (void)pipe_pass<T, CH, PS, false, DIA, false, AUG, NT, false, SH, PF>(pa, tiles_per_block, sh);
+  (void)pipe_pass<T, CH, PS, false, DIA, false, AUG, NT, false, SH, PF, EL>(pa, tiles_per_block, sh);
 }
 
 // ---- wave form: single-pass step for operators made of a few diagonals with ARBITRARY offsets (structured grids) ----
@@ -1356,7 +1399,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pipe_ring(const PipeArgsT<T> p
 template <class T, bool DIA, bool WAVE, bool AUG, bool RING, bool PF> constexpr int pipe_park_cols() {
   return (std::is_same<T, double>::value && DIA && !WAVE && !AUG && !RING && !PF) ? PIPE_PARK_COLS : 0;
 }
-template <class T, int CH, int WAVES, int PS, bool DIA, bool WAVE = false, bool AUG = false, bool NT = false, bool RING = false, bool PF = false>
+template <class T, int CH, int WAVES, int PS, bool DIA, bool WAVE = false, bool AUG = false, bool NT = false, bool RING = false, bool PF = false, bool EL = false>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_pipe_live(const PipeArgsT<T> pa, int tiles_per_block) {
   // (the 16- and the 24-column variant run at the same 3 workgroups per CU and follow each other in a factorisation: the same LDS
   //  size for both, so that a workgroup of step 17 fits the hole a workgroup of step 16 leaves -- with different sizes the first
@@ -1368,7 +1411,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pipe_live(const PipeArgsT<T> p
   if (threadIdx.x == 0)   // this workgroup is resident (see k_pipe_gate)
     (void)__hip_atomic_fetch_add(pa.arrive + (blockIdx.x % PIPE_FLAG_COPIES) * PIPE_ARRIVE_STRIDE, 1u, __ATOMIC_RELAXED,
                                  __HIP_MEMORY_SCOPE_AGENT);
-  const int r = pipe_pass<T, CH, PS, true, DIA, WAVE, AUG, NT, RING, SH, PF>(pa, tiles_per_block, sh);
+  const int r = pipe_pass<T, CH, PS, true, DIA, WAVE, AUG, NT, RING, SH, PF, EL>(pa, tiles_per_block, sh);
   if (r == 1 || r == 2) {   // last workgroup: publish the step (its results, stored through, first)
     PIPE_STAMP(pa.step, 5);
     EPI_STAMP(pa.step, 4);
@@ -1764,6 +1807,13 @@ static void pipe_launch(hipStream_t s, const PipeArgsT<T> &pa, int nbatch, int b
   if (nbatch > 1) tpb = (ntiles * nbatch + (int64_t)batch_rounds * maxb - 1) / ((int64_t)batch_rounds * maxb);
   if (tpb < 1) tpb = 1;
   const int nb = (int)((ntiles + tpb - 1) / tpb);
+  if constexpr (DIA && !AUG && !PF && std::is_same<T, double>::value) {      // constant tiles to elide: the EL instantiations (same occupancy by launch bounds)
+    if (pa.dia_mask != nullptr && nbatch == 1) {
+      if (pipe_nontemporal(pa, nbatch)) hipLaunchKernelGGL((k_pipe<T, CH, WAVES, PS, DIA, AUG, true, PF, true>), dim3(nb, nbatch), dim3(BLOCK), 0, s, pa, (int)tpb);
+      else hipLaunchKernelGGL((k_pipe<T, CH, WAVES, PS, DIA, AUG, false, PF, true>), dim3(nb, nbatch), dim3(BLOCK), 0, s, pa, (int)tpb);
+      return;
+    }
+  }
   if constexpr (DIA && !AUG && !PF && pipe_has_nt<T, CH>()) {
     if (pipe_nontemporal(pa, nbatch)) {
       hipLaunchKernelGGL((k_pipe<T, CH, WAVES, PS, DIA, AUG, true, PF>), dim3(nb, nbatch), dim3(BLOCK), 0, s, pa, (int)tpb);
@@ -1936,6 +1986,13 @@ static int pipe_live_launch(hipStream_t s, const PipeArgsT<T> &pa) {
   int64_t tpb = (ntiles + maxb - 1) / maxb;
   if (tpb < 1) tpb = 1;
   const int nb = (int)((ntiles + tpb - 1) / tpb);
+  if constexpr (DIA && !AUG && !PF && std::is_same<T, double>::value) {      // constant tiles to elide: the EL instantiations (same occupancy by launch bounds)
+    if (pa.dia_mask != nullptr) {
+      if (pipe_nontemporal(pa, 1)) hipLaunchKernelGGL((k_pipe_live<T, CH, WAVES, PS, DIA, false, AUG, true, false, PF, true>), dim3(nb), dim3(BLOCK), 0, s, pa, (int)tpb);
+      else hipLaunchKernelGGL((k_pipe_live<T, CH, WAVES, PS, DIA, false, AUG, false, false, PF, true>), dim3(nb), dim3(BLOCK), 0, s, pa, (int)tpb);
+      return nb;
+    }
+  }
   if constexpr (DIA && !AUG && !PF && pipe_has_nt<T, CH>()) {
     if (pipe_nontemporal(pa, 1)) {
       hipLaunchKernelGGL((k_pipe_live<T, CH, WAVES, PS, DIA, false, AUG, true, false, PF>), dim3(nb), dim3(BLOCK), 0, s, pa, (int)tpb);

@@ -103,6 +103,10 @@ int expv_mi_ctx_set_pipeline_overlap(expv_mi_ctx_t ctx, int on);
  *   "stencil" 0         banded fp64 operators whose stored diagonals are constant (constant-coefficient finite differences): apply
  *                       them from scalars instead of streaming the diagonals (bitwise the same result, 40 % less operator-side
  *                       traffic on a 5-diagonal operator); off by default so that a general sparse operator is timed as one
+ *   "elide" 1           banded fp64 operators, halo form of the single-pass step: a stored diagonal that holds ONE value on a whole tile of
+ *                       512 rows (found per tile and diagonal at creation and at every values update, expv_mi_op_elide_info) is read
+ *                       there as one entry instead of being streamed; bitwise the same result.  0: stream everything (EXPV_MI_ELIDE=0).
+ *                       "stencil" 1 on a wholly constant operator takes precedence
  *   "recycle" 1         expv_mi_ks_destroy keeps the storage of the subspace (one per context) and the next expv_mi_ks_create of
  *                       the same shape takes it over, reset to the freshly built state: the create-use-destroy pattern of the
  *                       convenience methods costs no hipMalloc / hipFree.  0: destroy frees at once
@@ -389,6 +393,11 @@ int expv_mi_op_reorder_info(expv_mi_op_t op, int64_t out[4]);
  * of the ring lengths, out[5] = tiles whose ring is longer than 128 rows, out[6] = column indices kept after sharing the equal
  * column blocks of slices, out[7] = ring entries stored per tile. */
 int expv_mi_op_patch_info(expv_mi_op_t op, int64_t out[8]);
+/* Constant tiles of a banded fp64 operator (context option "elide"): out[0] tiles of 512 stored rows, out[1] stored diagonals,
+ * out[2] (tile, diagonal) pairs on which the diagonal holds one bit pattern (zero fill included) and is therefore not streamed by
+ * the single-pass step, out[3] 1 = every diagonal is constant on all its rows (what option "stencil" needs).  mask (may be null):
+ * receives min(mask_len, out[0]) bytes, bit d of byte t = diagonal d on tile t.  All zero for operators without that form. */
+int expv_mi_op_elide_info(expv_mi_op_t op, int64_t out[4], unsigned char *mask, int64_t mask_len);
 /* Ordering plans by pattern (no reference counterpart: the reference applies A as stored, arnoldi.jl:185).  What creation derives from
  * the PATTERN of a sparse operator -- the row ordering, P A P' with the map back to the caller's entries, the rings and tile-local
  * columns of the patch form -- is kept for the last few patterns (process-wide; default 2, environment EXPV_MI_PLAN_CACHE at load

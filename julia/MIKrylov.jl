@@ -317,6 +317,15 @@ function patch_info(op::MIOperator)
     check(ccall((:expv_mi_op_patch_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), op.h, out), ctx().h)
     (patch_form = out[1] != 0, grid_row_length = out[2], tiles = out[3], longest_ring = out[4], mean_ring = out[3] > 0 ? out[5] / out[3] : 0.0)
 end
+# Banded Float64 operators (context option "elide", default on): the (tile of 512 stored rows, diagonal) pairs on which the stored diagonal
+# holds one value and is read as one entry instead of being streamed; mask[t] bit d-1 = diagonal d on tile t.
+function elide_info(op::MIOperator)
+    out = zeros(Int64, 4)
+    check(ccall((:expv_mi_op_elide_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}, Int64), op.h, out, C_NULL, 0), ctx().h)
+    mask = zeros(UInt8, out[1])
+    isempty(mask) || check(ccall((:expv_mi_op_elide_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}, Int64), op.h, out, mask, length(mask)), ctx().h)
+    (tiles = out[1], diagonals = out[2], constant_pairs = out[3], wholly_constant = out[4] != 0, mask = mask)
+end
 MIOperator(A::SparseMatrixCSC{T}) where {T <: MIScalar} = MIOperator(SparseMatrixCSC{T, Int64}(A))      # (other index types: converted once)
 # A' and transpose(A) of an operator that exists (expv_mi_op_create_adjoint): the reference's expv(t, A', b), where A' is a lazy
 # wrapper and mul! does the rest (arnoldi.jl:185) -- the call of an adjoint sensitivity and of a left eigenvector.  Here the
