@@ -15,6 +15,7 @@ BLOCK_COL_MAJOR, BLOCK_ROW_MAJOR = 0, 1      # EXPV_MI_BLOCK_*: element (i, k) a
 BSR_BLOCK_ROW_MAJOR, BSR_BLOCK_COL_MAJOR, BSR_COMPRESSED_COLS = 0, 1, 2      # layout bits of expv_mi_op_create_bsr_loc
 DIA_ALIGN_COL, DIA_ALIGN_ROW, DIA_ALIGN_START = 0, 1, 2                      # align of expv_mi_op_create_dia_loc
 OP_TRANSPOSE, OP_ADJOINT = 1, 2                                              # how of expv_mi_op_create_adjoint
+LINCOMB_MAX_TERMS, LINCOMB_IDENTITY = 8, 1                                   # cap and flag of expv_mi_op_create_lincomb
 ORTHO_AUTO, ORTHO_MGS, ORTHO_LOWSYNC, ORTHO_PIPELINED = 0, 1, 2, 3
 PATH_FLAGS = {"modular": 1, "two_kernel": 2, "pipeline": 4, "wave": 8, "overlapped": 16, "redo_serial": 32,
               "redo_wave_off": 64, "resident": 128, "patch": 256, "pipelined_lanczos": 512}
@@ -96,6 +97,8 @@ PROTOTYPES = {
     "expv_mi_op_create_dia_loc": (_i, [_vp, _i, _i64, _i, _vp, _vp, _i64, _i, _i, _pvp]),
     "expv_mi_op_create_adjoint": (_i, [_vp, _i, _pvp]),
     "expv_mi_op_adjoint_refresh": (_i, [_vp, _vp]),
+    "expv_mi_op_create_lincomb": (_i, [_i, _vp, _vp, _i, _pvp]),
+    "expv_mi_op_lincomb_refresh": (_i, [_vp, _i, _vp, _vp]),
     "expv_mi_op_ingest_info": (_i, [_vp, _vp]),
     "expv_mi_op_create_dense": (_i, [_vp, _i, _i64, _vp, _i64, _i, _pvp]),
     "expv_mi_op_create_callback": (_i, [_vp, _i, _i64, MATVEC_FN, _vp, _i, _i64, _pvp]),

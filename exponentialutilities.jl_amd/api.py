@@ -187,6 +187,11 @@ def _is_torch(x):
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
 
 
+def _is_scalar(c):
+    """a Python or numpy number (not a bool): what multiplies an operator"""
+    return isinstance(c, (int, float, complex, np.number)) and not isinstance(c, (bool, np.bool_))
+
+
 def _np_dtype_of(x):
     if isinstance(x, DeviceArray):
         return x.dtype
@@ -601,7 +606,9 @@ class MIOperator:
     constructor or front ends keeps going through ``.tocsc()``.  Stored diagonals (a scipy ``dia_matrix``, or a 2-D tensor / array
     with one row per diagonal and the offsets) come in through ``MIOperator.from_dia`` (expv_mi_op_create_dia_loc); the plain
     constructor treats a scipy ``dia_matrix`` as before.  ``A.adjoint()`` / ``A.transpose()`` (``A.H`` / ``A.T``) build the operator
-    of ``A'`` / ``transpose(A)`` on the device from what ``A`` stores (expv_mi_op_create_adjoint): ``expv(t, A.H, b)``.  Exposes
+    of ``A'`` / ``transpose(A)`` on the device from what ``A`` stores (expv_mi_op_create_adjoint): ``expv(t, A.H, b)``.  ``A + B``, ``A - B``, ``-A``, ``c * A``, ``A / c`` and
+    ``MIOperator.lincomb(terms, coefs, identity=None)`` build linear combinations there too (expv_mi_op_create_lincomb), and
+    ``C.recombine(coefs)`` changes the coefficients of one: ``expv(t, H0 + f * H1, b)``.  Exposes
     ``shape``, ``dtype``, ``ishermitian`` (LinearAlgebra.ishermitian), ``nnz`` and ``opnorm_inf``.
     """
 
@@ -971,6 +978,9 @@ class MIOperator:
         if getattr(self, "_adj_how", 0) and (_is_torch_sparse(A) or hasattr(A, "indptr")):
             raise TypeError("update_values: an operator made by adjoint() / transpose() takes bare values in its own sorted-row order; "
                             "to follow its parent use refresh(parent), for another element type parent.astype(dtype).adjoint()")
+        if getattr(self, "_lc_terms", None) is not None and (_is_torch_sparse(A) or hasattr(A, "indptr")):
+            raise TypeError("update_values: an operator made by lincomb() (or by + - * /) takes bare values in its own sorted-row order; "
+                            "to follow its terms or change its coefficients use recombine(coefs)")
         if fmt == "coo":
             return self._update_coo(A)
         if fmt == "bsr":
@@ -1156,10 +1166,128 @@ class MIOperator:
         self._read_info()
         return self
 
+    # ---- linear combinations of operators that exist (expv_mi_op_create_lincomb / expv_mi_op_lincomb_refresh) ----
+    @staticmethod
+    def _lincomb_args(terms, coefs, identity, who):
+        terms, coefs = list(terms), list(coefs)
+        for t in terms:
+            if not isinstance(t, MIOperator):
+                raise TypeError("%s: every term must be an MIOperator, not %s" % (who, type(t).__name__))
+        if len(coefs) != len(terms):
+            raise ValueError("%s: one coefficient per term expected (%d terms, %d coefficients)" % (who, len(terms), len(coefs)))
+        for c in coefs + ([] if identity is None else [identity]):
+            if not _is_scalar(c):
+                raise TypeError("%s: a coefficient must be a scalar, not %s" % (who, type(c).__name__))
+        pairs = np.zeros(2 * (len(coefs) + (identity is not None)), dtype=np.float64)
+        for k, c in enumerate(coefs + ([] if identity is None else [identity])):
+            c = complex(c)
+            pairs[2 * k], pairs[2 * k + 1] = c.real, c.imag
+        handles = (C.c_void_p * max(len(terms), 1))(*[t._h for t in terms])
+        return terms, pairs, handles
+
+    @staticmethod
+    def lincomb(terms, coefs, identity=None):
+        """``coefs[0] * terms[0] + ... + coefs[K-1] * terms[K-1] (+ identity * I)`` as a NEW, independent ``MIOperator`` on the
+        terms' context (expv_mi_op_create_lincomb), K <= 8: the reference's ``expv(t, H0 + f*H1, b)`` and ``expv(t, A - sigma*I, b)``.
+        Built on the device from what the terms store -- all sparse (of any birth, reordered or not) or all dense, one element type
+        and size; the values never visit the host.  The pattern is the union of the terms' patterns (plus the diagonal when
+        ``identity`` is given), whatever the values and coefficients are: cancelled entries stay stored.  The values are summed in
+        term order, the identity last, nothing fused (include/expv_mi.h states the roundings).  This is the one-pass form for
+        more than two terms: ``A + B + C`` builds ``A + B`` first.  ``recombine`` changes the coefficients, or follows the terms'
+        values, at the cost of one kernel and a value refill.  As for ``adjoint()``: ``src`` is ``None``, ``astype`` is refused,
+        ``update_values`` takes bare values in the result's own sorted-row order."""
+        terms, pairs, handles = MIOperator._lincomb_args(terms, coefs, identity, "lincomb")
+        if not terms:
+            raise ValueError("lincomb: one term at least (the identity alone has no context, element type or size)")
+        lib = L.load()
+        h = C.c_void_p()
+        ctx = terms[0].ctx
+        _check(lib.expv_mi_op_create_lincomb(len(terms), handles, pairs.ctypes.data, L.LINCOMB_IDENTITY if identity is not None else 0,
+                                             C.byref(h)), ctx._h)
+        op = object.__new__(MIOperator)
+        op.ctx, op.src, op._cb, op._matvec, op._h = ctx, None, None, None, h
+        op._finalizer = weakref.finalize(op, lib.expv_mi_op_destroy, h)
+        op._lc_terms, op._lc_identity = terms, identity
+        op.src_dtype = terms[0].src_dtype
+        if all(getattr(t, "_sp_format", None) is not None for t in terms):      # sparse: bare values refresh it in its own sorted-row order
+            op._sp_format, op._sp_sorted = "csr", True
+        op._read_info()
+        return op
+
+    def recombine(self, coefs, terms=None, identity=None):
+        """Of an operator made by ``lincomb`` (or by ``+``, ``-``, ``*``, ``/``): new coefficients and the CURRENT values of the
+        terms -- by default the ones kept from creation, else operators of the same patterns -- on the device
+        (expv_mi_op_lincomb_refresh); ``ishermitian`` / ``opnorm_inf`` are re-evaluated.  Bit-equal to ``lincomb`` made anew.
+        ``identity`` may only be given when the operator was created with one (its coefficient then defaults to the last one
+        given).  Another pattern with the same counts is the caller's error."""
+        kept = getattr(self, "_lc_terms", None)
+        if kept is None:
+            raise TypeError("recombine: only an operator made by lincomb() (or by + - * /) recombines")
+        had = self._lc_identity is not None
+        if identity is not None and not had:
+            raise ValueError("recombine: the operator was made without the identity; its pattern holds no diagonal for one")
+        if had and identity is None:
+            identity = self._lc_identity
+        terms, pairs, handles = MIOperator._lincomb_args(kept if terms is None else terms, coefs, identity, "recombine")
+        _check(L.load().expv_mi_op_lincomb_refresh(self._h, len(terms), handles, pairs.ctypes.data), self.ctx._h)
+        self._lc_terms, self._lc_identity = terms, identity
+        self._read_info()
+        return self
+
+    __array_ufunc__ = None      # numpy leaves `array * A` and `scalar + A` to the methods below
+
+    def _lc_other(self, other, sign, what):
+        if not isinstance(other, MIOperator):
+            hint = " (for a shift use MIOperator.lincomb([A], [1], identity=sigma))" if _is_scalar(other) else ""
+            raise TypeError("%s: the other side must be an MIOperator, not %s%s" % (what, type(other).__name__, hint))
+        return MIOperator.lincomb([self, other], [1.0, sign])
+
+    def _lc_scaled(self, c, what):
+        if not _is_scalar(c):
+            raise TypeError("%s: the other side must be a scalar, not %s" % (what, type(c).__name__))
+        return MIOperator.lincomb([self], [c])
+
+    def __add__(self, other):
+        """``A + B``: a new operator at every evaluation (the ``.H`` convention), ``lincomb([A, B], [1, 1])``"""
+        return self._lc_other(other, 1.0, "A + B")
+
+    def __radd__(self, other):
+        return self._lc_other(other, 1.0, "B + A")
+
+    def __sub__(self, other):
+        """``A - B``: ``lincomb([A, B], [1, -1])``; ``A - A`` keeps the entries of ``A`` as stored zeros"""
+        return self._lc_other(other, -1.0, "A - B")
+
+    def __rsub__(self, other):
+        raise TypeError("B - A: the other side must be an MIOperator, not %s" % type(other).__name__)
+
+    def __neg__(self):
+        """``-A``: ``lincomb([A], [-1])``"""
+        return MIOperator.lincomb([self], [-1.0])
+
+    def __mul__(self, c):
+        """``A * c`` and ``c * A``: ``lincomb([A], [c])``"""
+        return self._lc_scaled(c, "A * c")
+
+    def __rmul__(self, c):
+        return self._lc_scaled(c, "c * A")
+
+    def __truediv__(self, c):
+        """``A / c``: ``lincomb([A], [1 / c])`` -- the reciprocal is rounded first, then every entry multiplied"""
+        if not _is_scalar(c):
+            raise TypeError("A / c: the other side must be a scalar, not %s" % type(c).__name__)
+        return MIOperator.lincomb([self], [1.0 / c])
+
+    def __rtruediv__(self, c):
+        raise TypeError("c / A: an operator has no reciprocal")
+
     def astype(self, dtype):
         dtype = _work_dtype(dtype)
         if dtype == self.dtype:
             return self
+        if getattr(self, "_lc_terms", None) is not None:
+            raise TypeError("an operator made by lincomb() (or by + - * /) keeps no source to convert: combine the converted terms, "
+                            "MIOperator.lincomb([t.astype(dtype) for t in terms], coefs)")
         if getattr(self, "_adj_how", 0):
             raise TypeError("an operator made by adjoint() / transpose() keeps no source to convert: use parent.astype(dtype).adjoint() "
                             "(and refresh(parent.astype(dtype)) after the parent changes)")

@@ -13,6 +13,7 @@
 #include <unordered_map>
 
 #include "engine.h"
+#include "op_lincomb.h"
 #include "reorder.h"
 
 using namespace expv_mi;
@@ -2460,6 +2461,215 @@ int expv_mi_op_adjoint_refresh(expv_mi_op_t adj, expv_mi_op_t parent) {
     dispatch_host_dtype(adj->dtype, [&](auto tag) {
       using V = typename decltype(tag)::type;
       op_update_values_T<typename DevOf<V>::type, V>(*adj, adj->adj_val.p, EXPV_MI_DEVICE);
+    });
+  });
+}
+
+// ---- linear combinations of operators that exist: c_1 A_1 + ... + c_K A_K (+ c_I I) (kernels: op_lincomb.hip) ------------------------
+static_assert(dev::LINCOMB_MAX_TERMS == EXPV_MI_LINCOMB_MAX_TERMS, "the kernels' term table and the header agree on the cap");
+
+// the term table the value kernels take in their arguments; coef: (re, im) pairs, the identity's last, each rounded once here
+extern "C++" {
+template <class T>
+static dev::LincombTerms<T> lincomb_table(int nterms, const expv_mi_op_t *terms, const double *coef, bool identity, bool dense) {
+  using R = typename ST<T>::real_t;
+  dev::LincombTerms<T> a;
+  std::memset(&a, 0, sizeof(a));
+  a.nterms = nterms;
+  a.identity = identity ? 1 : 0;
+  for (int k = 0; k <= dev::LINCOMB_MAX_TERMS; ++k) a.off[k] = INT32_MAX;
+  int64_t off = 0;
+  for (int k = 0; k < nterms; ++k) {
+    const Op &t = *terms[k];
+    a.val[k] = dense ? reinterpret_cast<const T *>(t.dense_ptr) : t.val.as<T>();
+    a.lda[k] = t.lda;
+    a.off[k] = (int32_t)off;
+    if (!dense) off += t.nnz;
+  }
+  a.off[nterms] = (int32_t)off;      // (create_lincomb checked: off + n fits 31 bits)
+  for (int k = 0; k < nterms + (identity ? 1 : 0); ++k) {
+    a.cre[k] = (R)coef[2 * k];
+    a.cim[k] = (R)coef[2 * k + 1];
+  }
+  return a;
+}
+}  // extern "C++"
+
+// the checks of the coefficients that creation and refresh share
+static void lincomb_check_coef(const std::string &who, int dtype, int npairs, const double *coef) {
+  const bool real = dtype == EXPV_MI_F64 || dtype == EXPV_MI_F32;
+  for (int k = 0; k < npairs; ++k)
+    if (real && coef[2 * k + 1] != 0.0) fail(EXPV_MI_ARGUMENT_ERROR, who + ": a coefficient with a nonzero imaginary part for a real element type");
+  for (int k = 0; k < 2 * npairs; ++k)
+    if (!std::isfinite(coef[k])) fail(EXPV_MI_ARGUMENT_ERROR, who + ": a coefficient that is not finite");
+}
+
+// Sparse: the terms' stored entries (and the identity's) -> (p[row], p[col]) keys with the position in the concatenation as payload
+// -> the stable sort, the heads and the compression of the triplet path -> the union pattern in the natural ordering, the map and
+// the segment table; one gather-scale-sum launch makes the values; then the tail of every device-born operator.
+static void create_lincomb_sparse(Ctx *ctx, int nterms, const expv_mi_op_t *terms, const double *coef, bool identity, expv_mi_op_t *out) {
+  const std::string who = "op_create_lincomb";
+  const auto t_begin = std::chrono::steady_clock::now();
+  hipStream_t s = ctx->stream;
+  const int dtype = terms[0]->dtype;
+  const int64_t n = terms[0]->n;
+  const size_t vbytes = dtype_size(dtype);
+  int64_t total = identity ? n : 0;
+  for (int k = 0; k < nterms; ++k) total += terms[k]->nnz;
+  DevBuf key[2], pay[2], hist, part, st_dev(sizeof(dev::CooStatus));
+  DevBuf ptr32(sizeof(int32_t) * (size_t)(n + 1));
+  int passes = 0;
+  int64_t stored = 0;
+  if (total > 0) {
+    for (int z = 0; z < 2; ++z) {
+      key[z].alloc(sizeof(unsigned long long) * (size_t)total + 16);
+      pay[z].alloc(sizeof(int32_t) * (size_t)total + 16);
+    }
+    hist.alloc(sizeof(uint32_t) * (size_t)dev::coo_hist_words(total));
+    int64_t base = 0;
+    for (int k = 0; k < nterms; ++k) {
+      const Op &t = *terms[k];
+      dev::lincomb_keys(s, t.rowptr.as<int32_t>(), t.col.as<int32_t>(), t.perm ? t.perm->p.as<int32_t>() : nullptr, n, t.nnz, base,
+                        key[0].as<unsigned long long>(), pay[0].as<int32_t>());
+      base += t.nnz;
+    }
+    if (identity) dev::lincomb_identity_keys(s, n, base, key[0].as<unsigned long long>(), pay[0].as<int32_t>());
+    unsigned long long *kp[2] = {key[0].as<unsigned long long>(), key[1].as<unsigned long long>()};
+    int32_t *pp[2] = {pay[0].as<int32_t>(), pay[1].as<int32_t>()};
+    passes = dev::coo_sort(s, n, total, kp, pp, hist.as<uint32_t>());      // (0 passes for n = 1: the key kernels wrote the identity payload)
+    part.alloc(sizeof(uint32_t) * (size_t)dev::coo_scan_words(total));
+    dev::coo_count_heads(s, key[passes & 1].as<unsigned long long>(), total, part.as<uint32_t>(), st_dev.as<dev::CooStatus>());
+    unsigned long long cnt = 0;
+    HIPCHECK(hipMemcpyAsync(&cnt, &st_dev.as<dev::CooStatus>()->stored, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    stored = (int64_t)cnt;
+    if (stored < 1 || stored > total) fail(EXPV_MI_ASSERTION, who + ": bad count of distinct coordinates");
+  }
+  DevBuf &skey = key[passes & 1], &src = pay[passes & 1];
+  DevBuf idx32(sizeof(int32_t) * (size_t)std::max<int64_t>(stored, 1) + 16), seg(sizeof(int32_t) * (size_t)(stored + 1)),
+      pval(vbytes * (size_t)std::max<int64_t>(stored, 1) + 16);
+  if (total > 0) {
+    dev::coo_compress(s, skey.as<unsigned long long>(), n, total, stored, part.as<uint32_t>(), ptr32.as<int32_t>(), idx32.as<int32_t>(), seg.as<int32_t>());
+    dispatch_host_dtype(dtype, [&](auto tag) {
+      using T = typename DevOf<typename decltype(tag)::type>::type;
+      dev::lincomb_gather<T>(s, lincomb_table<T>(nterms, terms, coef, identity, false), src.as<int32_t>(), seg.as<int32_t>(), stored, pval.as<T>());
+    });
+  } else {
+    HIPCHECK(hipMemsetAsync(ptr32.p, 0, ptr32.bytes, s));
+  }
+  HIPCHECK(hipStreamSynchronize(s));
+  const auto t_ingest = std::chrono::steady_clock::now();
+  key[0].release();
+  key[1].release();
+  pay[(passes & 1) ^ 1].release();
+  hist.release();
+  part.release();
+  // rows strictly ascending: one stored entry per distinct coordinate
+  finish_sparse_device(ctx, who, false, dtype, n, stored, ptr32, idx32, pval.p, true, t_begin,
+                       (int64_t)std::chrono::duration<double, std::micro>(t_ingest - t_begin).count(),
+                       [&](Op &op) {      // what expv_mi_op_lincomb_refresh gathers through
+                         op.lc_nterms = nterms;
+                         op.lc_identity = identity;
+                         for (int k = 0; k < nterms; ++k) op.lc_nnz[k] = terms[k]->nnz;
+                         if (total > 0) {
+                           op.lc_src = std::move(src);
+                           op.lc_seg = std::move(seg);
+                         }
+                       },
+                       out);
+}
+
+// Dense: an owned packed matrix of the combination, then the property pass of a device-resident dense operator.
+static void create_lincomb_dense(Ctx *ctx, int nterms, const expv_mi_op_t *terms, const double *coef, bool identity, expv_mi_op_t *out) {
+  const int dtype = terms[0]->dtype;
+  const int64_t n = terms[0]->n;
+  const size_t esz = dtype_size(dtype);
+  std::unique_ptr<expv_mi_op_s> op(new expv_mi_op_s());
+  op->ctx = ctx;
+  op->device = ctx->device;
+  op->dtype = dtype;
+  op->kind = OP_DENSE;
+  op->n = n;
+  op->dense.alloc((size_t)std::max<int64_t>(n * n, 1) * esz);
+  dispatch_host_dtype(dtype, [&](auto tag) {
+    using T = typename DevOf<typename decltype(tag)::type>::type;
+    dev::lincomb_dense<T>(ctx->stream, lincomb_table<T>(nterms, terms, coef, identity, true), n, op->dense.as<T>());
+  });
+  op->dense_ptr = op->dense.p;
+  op->lda = n;
+  op->nnz = n * n;
+  op->ishermitian = n == 0 ? 1 : 0;
+  op->opnorm_inf = 0.0;
+  op->lc_nterms = nterms;
+  op->lc_identity = identity;
+  dense_split_and_props(ctx, *op);
+  ctx->adopt(&op->ctx);
+  *out = op.release();
+}
+
+int expv_mi_op_create_lincomb(int nterms, const expv_mi_op_t *terms, const double *coef, int flags, expv_mi_op_t *out) {
+  const bool count_ok = nterms >= 1 && nterms <= EXPV_MI_LINCOMB_MAX_TERMS;
+  Ctx *ctx = (nterms >= 1 && terms && terms[0]) ? terms[0]->ctx : nullptr;      // (where a failure's message goes: the first term's context, if any)
+  return guarded(ctx, [&] {
+    const std::string who = "op_create_lincomb";
+    if (!out) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null output");
+    if (flags & ~EXPV_MI_LINCOMB_IDENTITY) fail(EXPV_MI_ARGUMENT_ERROR, who + ": unknown flag bits");
+    if (!count_ok)
+      fail(EXPV_MI_ARGUMENT_ERROR, who + ": nterms must be 1 .. 8 (the identity alone has no term to take a context, an element type and n from)");
+    if (!coef) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null coef");
+    if (!terms) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null terms");
+    for (int k = 0; k < nterms; ++k)
+      if (!terms[k] || !terms[k]->ctx) fail(EXPV_MI_ARGUMENT_ERROR, who + ": a null term, or a term whose context is gone");
+    for (int k = 1; k < nterms; ++k)
+      if (terms[k]->ctx != ctx || terms[k]->dtype != terms[0]->dtype || terms[k]->n != terms[0]->n)
+        fail(EXPV_MI_ARGUMENT_ERROR, who + ": the terms differ in context, dtype or n");
+    for (int k = 0; k < nterms; ++k)
+      if (terms[k]->kind == OP_CALLBACK) fail(EXPV_MI_UNSUPPORTED, who + ": a matrix-free operator stores nothing to combine");
+    for (int k = 1; k < nterms; ++k)
+      if (terms[k]->kind != terms[0]->kind) fail(EXPV_MI_ARGUMENT_ERROR, who + ": sparse and dense terms do not mix");
+    const bool identity = (flags & EXPV_MI_LINCOMB_IDENTITY) != 0;
+    lincomb_check_coef(who, terms[0]->dtype, nterms + (identity ? 1 : 0), coef);
+    if (terms[0]->kind == OP_CSR) {
+      int64_t total = identity ? terms[0]->n : 0;
+      for (int k = 0; k < nterms; ++k) total += terms[k]->nnz;
+      if (total > 0x7fffffffLL) fail(EXPV_MI_ARGUMENT_ERROR, who + ": the terms' entries (and the diagonal) exceed 2^31 - 1");
+    }
+    ctx->use();
+    if (terms[0]->kind == OP_DENSE) create_lincomb_dense(ctx, nterms, terms, coef, identity, out);
+    else create_lincomb_sparse(ctx, nterms, terms, coef, identity, out);
+  });
+}
+
+int expv_mi_op_lincomb_refresh(expv_mi_op_t op, int nterms, const expv_mi_op_t *terms, const double *coef) {
+  Ctx *ctx = op ? op->ctx : nullptr;
+  return guarded(ctx, [&] {
+    const std::string who = "op_lincomb_refresh";
+    if (!op) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null operator");
+    if (!ctx) fail(EXPV_MI_ARGUMENT_ERROR, who + ": the context is gone");
+    if (op->lc_nterms == 0) fail(EXPV_MI_ARGUMENT_ERROR, who + ": not created by op_create_lincomb");
+    if (nterms != op->lc_nterms) fail(EXPV_MI_ARGUMENT_ERROR, who + ": another number of terms than the operator was made from");
+    if (!coef || !terms) fail(EXPV_MI_ARGUMENT_ERROR, who + ": null terms / coef");
+    for (int k = 0; k < nterms; ++k) {
+      if (!terms[k] || !terms[k]->ctx) fail(EXPV_MI_ARGUMENT_ERROR, who + ": a null term, or a term whose context is gone");
+      if (terms[k]->ctx != ctx) fail(EXPV_MI_ARGUMENT_ERROR, who + ": a term lives on another context");
+      if (terms[k]->kind != op->kind || terms[k]->dtype != op->dtype || terms[k]->n != op->n || (op->kind == OP_CSR && terms[k]->nnz != op->lc_nnz[k]))
+        fail(EXPV_MI_ARGUMENT_ERROR, who + ": a term differs in kind, dtype, n or nnz from the one the operator was made from");
+    }
+    lincomb_check_coef(who, op->dtype, nterms + (op->lc_identity ? 1 : 0), coef);
+    ctx->use();
+    dispatch_host_dtype(op->dtype, [&](auto tag) {
+      using V = typename decltype(tag)::type;
+      using T = typename DevOf<V>::type;
+      if (op->kind == OP_DENSE) {
+        dev::lincomb_dense<T>(ctx->stream, lincomb_table<T>(nterms, terms, coef, op->lc_identity, true), op->n, op->dense.as<T>());
+        dense_split_and_props(ctx, *op);
+        return;
+      }
+      if (op->nnz == 0) return;
+      if (!op->lc_val.p) op->lc_val.alloc(sizeof(T) * (size_t)op->nnz + 16);
+      dev::lincomb_gather<T>(ctx->stream, lincomb_table<T>(nterms, terms, coef, op->lc_identity, false), op->lc_src.as<int32_t>(), op->lc_seg.as<int32_t>(),
+                             op->nnz, op->lc_val.as<T>());
+      op_update_values_T<T, V>(*op, op->lc_val.p, EXPV_MI_DEVICE);
     });
   });
 }

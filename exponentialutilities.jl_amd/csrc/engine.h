@@ -350,7 +350,16 @@ struct Op {
   // through) and, from the first refresh on, the buffer the gathered values go to.  Dense: `dense` is the owned packed copy.
   int adj_how = 0;
   DevBuf adj_src, adj_val;
-  bool plan_cached = false;      // the ordering / patch plan came from the process-wide plan cache (capi.hip: OrderPlanCache)
+  // lincomb-born (capi.hip: create_lincomb): the number of terms (0: not lincomb-born), whether the identity was one more, and the
+  // stored entries of each term.  Sparse: lc_src[q] = position, in the concatenation of the terms' stored arrays (the identity's n
+  // entries last), behind sorted position q; lc_seg[e] .. lc_seg[e + 1] - 1 = sorted positions of stored entry e (what a refresh
+  // gathers, scales and sums through: 4 (sum nnz_k [+ n] + nnz + 1) bytes) and, from the first refresh on, the buffer the sums go
+  // to.  Dense: `dense` is the owned packed matrix.
+  int lc_nterms = 0;
+  bool lc_identity = false;
+  int64_t lc_nnz[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  DevBuf lc_src, lc_seg, lc_val;
+  bool plan_cached = false;     // the ordering / patch plan came from the process-wide plan cache (capi.hip: OrderPlanCache)
   int64_t ring_sum = 0, ring_over128 = 0, ring_tiles = 0;      // sum of the ring lengths, tiles with a ring of more than 128 rows, tiles
   int ring_pad = 0;          // 0: no patch form
   int ring_max = 0;          // longest ring of a tile

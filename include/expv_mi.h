@@ -339,6 +339,50 @@ int expv_mi_op_create_dia_loc(expv_mi_ctx_t ctx, int dtype, int64_t n, int ndiag
 #define EXPV_MI_OP_ADJOINT   2   /* A' = conj(transpose(A)); real types: same bits as TRANSPOSE */
 int expv_mi_op_create_adjoint(expv_mi_op_t parent, int how, expv_mi_op_t *op);
 int expv_mi_op_adjoint_refresh(expv_mi_op_t adj, expv_mi_op_t parent);
+/* The operator C = c_1 A_1 + ... + c_K A_K (+ c_I I) of operators that exist, 1 <= K <= EXPV_MI_LINCOMB_MAX_TERMS -- the reference's
+ * expv(t, H0 + f(tk)*H1, b) and expv(t, A - sigma*I, b), where + and * on a sparse matrix make the sum: a driven Hamiltonian, the
+ * Jacobian J0 + c(u) J1 of an exponential integrator, a shifted operator.  The result is an INDEPENDENT operator on the terms'
+ * context with its own storage, built on the device from what the terms STORE: they may be updated or destroyed afterwards, and
+ * neither their values nor the combined ones visit the host.  `coef` holds (re, im) pairs, one per term, plus one more for the
+ * identity when EXPV_MI_LINCOMB_IDENTITY is set in `flags`; each is rounded once to the real type of the operator's elements.
+ *   - Pattern.  Decided by the terms' patterns and the flag alone, never by a value or a coefficient: the union of the terms'
+ *     coordinates, plus the whole diagonal with EXPV_MI_LINCOMB_IDENTITY, in the caller's natural ordering, every row sorted and
+ *     free of repeats.  An entry that cancels to zero stays stored; a term with coefficient 0 still contributes its pattern and
+ *     its products (0 * NaN is NaN); nnz is the number of distinct coordinates.
+ *   - Which operator.  BY DEFINITION the one expv_mi_op_create_csr_loc makes, on the same context, of those zero-based CSR32
+ *     arrays: the same planners, its own reordering decision, the plan cache keyed by the COMBINED pattern.  Only that pattern
+ *     comes to the host; expv_mi_op_ingest_info reports as for the adjoint: out[0] = 1, out[1] = 4 (n + 1 + nnz), out[2] = 0,
+ *     out[3 .. 5] as usual, out[6] = out[7] = 0.
+ *   - Values, bit for bit.  The contributions to one coordinate are added left to right in term order; inside a term that repeats
+ *     a coordinate, in that term's stored order; the identity comes last.  The accumulator STARTS as the first contribution, not
+ *     as 0, so -0 survives.  A coefficient with im == 0 multiplies each real component once; a complex one gives
+ *     (cr ar - ci ai, cr ai + ci ar), each product rounded, then the sum or difference rounded; the identity contributes its
+ *     coefficient (cr, ci) as it is.  Nothing is fused and no floating-point atomic is used: two creations give the same bits.
+ *   - Terms.  All sparse or all dense, on one context, of one dtype and n.  A sparse term may be of any birth, reordered (its
+ *     stored indices are relabelled through its permutation on the device first) or in patch form; the same handle may appear
+ *     twice; A + A' takes the operator expv_mi_op_create_adjoint made as a term.  All four element types.  Dense terms: the
+ *     result owns a packed (leading dimension n) column-major matrix written by one element-wise kernel -- 16-byte packs where the
+ *     address and the term's lda allow, rows n .. lda - 1 of a term are never read -- and goes through the property pass of
+ *     expv_mi_op_create_dense(..., EXPV_MI_DEVICE); the identity touches the diagonal only.
+ *   - Checks before any device work, EXPV_MI_ARGUMENT_ERROR "op_create_lincomb: ...", in this order: null output; unknown flag
+ *     bits; nterms outside [1, 8] (the identity without a term is refused too: this call has nothing to take a context, an element
+ *     type and n from); null coef; null terms; a null term, or one whose context is gone; terms on different contexts, or of
+ *     different dtype or n; a matrix-free term (EXPV_MI_UNSUPPORTED); sparse and dense terms mixed; a nonzero imaginary
+ *     coefficient for a real dtype; a coefficient that is not finite; for sparse terms, sum of nnz_k (+ n) > 2^31 - 1.  *op is
+ *     untouched on every failure.
+ *   - expv_mi_op_update_values on a sparse result takes nnz values in ITS OWN sorted-row order.
+ * expv_mi_op_lincomb_refresh(op, nterms, terms, coef) takes new coefficients and the terms' CURRENT values -- the terms it was made
+ * from, or others of the same patterns.  Sparse: one gather-scale-sum launch through the map the operator keeps, into a buffer it
+ * keeps, then the path of expv_mi_op_update_values, so ishermitian and opnorm(C, Inf) are re-evaluated; dense: the element-wise
+ * kernel again.  The result is bit for bit what expv_mi_op_create_lincomb would make anew.  EXPV_MI_ARGUMENT_ERROR
+ * "op_lincomb_refresh: ...": a null handle, op not lincomb-born, another nterms, a term on another context or of another kind,
+ * dtype, n or (sparse) nnz than the term in its place had, a bad coefficient.  Terms with the same counts but ANOTHER PATTERN are
+ * the caller's error and are not detected, as for expv_mi_op_update_values.  Kept on a sparse result for this: 4 (sum of nnz_k
+ * [+ n] + nnz + 1) bytes of map and segment table and, from the first refresh on, a buffer of nnz values. */
+#define EXPV_MI_LINCOMB_MAX_TERMS 8
+#define EXPV_MI_LINCOMB_IDENTITY  1   /* flags: coef carries one more pair, the identity's */
+int expv_mi_op_create_lincomb(int nterms, const expv_mi_op_t *terms, const double *coef, int flags, expv_mi_op_t *op);
+int expv_mi_op_lincomb_refresh(expv_mi_op_t op, int nterms, const expv_mi_op_t *terms, const double *coef);
 /* How a sparse operator came to be: out[0] 1 = created from device arrays (or triplets); out[1] bytes of pattern brought to the
  * host; out[2] bytes of VALUES brought to the host (0 when every row is sorted and free of duplicates); out[3] the whole creation
  * and out[4] the ingest kernels + status read-back (triplets: check, sort, compress and sums, by device events), in microseconds;

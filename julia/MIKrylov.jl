@@ -351,6 +351,59 @@ function LinearAlgebra.adjoint!(dest::MIOperator{T}, parent::MIOperator{T}) wher
     dest.opnorm_inf = on[]
     dest
 end
+# Linear combinations of operators that exist (expv_mi_op_create_lincomb): the reference's expv(t, H0 + f(tk)*H1, b) and
+# expv(t, A - sigma*I, b), where + and * on a sparse matrix make the sum.  Here the result is a NEW, independent MIOperator built on
+# the device from what the terms store (all sparse, of any birth, or all dense; one element type and size); the values never visit the
+# host.  The pattern is the union of the terms' patterns (plus the diagonal with an identity term), whatever the values are --
+# cancelled entries stay stored --, the values are added in term order, the identity last, nothing fused (include/expv_mi.h).
+# lincomb(terms, coefs; identity) is the one-pass form for more than two terms (A + B + C builds A + B first); recombine! gives
+# an operator made here new coefficients and the terms' current values for the cost of one kernel and a value refill.
+const LINCOMB_IDENTITY = Cint(1)
+const LINCOMB_KEPT = WeakKeyDict{Any, Any}()      # result => (terms, whether it holds the identity's diagonal)
+function lincomb_pairs(coefs, identity)
+    cs = identity === nothing ? collect(Number, coefs) : vcat(collect(Number, coefs), identity)
+    pairs = Vector{Cdouble}(undef, 2 * length(cs))
+    for (k, c) in enumerate(cs)
+        pairs[2k - 1], pairs[2k] = real(c), imag(c)
+    end
+    pairs
+end
+function lincomb(terms::AbstractVector{MIOperator{T}}, coefs; identity = nothing) where {T}
+    length(coefs) == length(terms) || throw(DimensionMismatch("lincomb: one coefficient per term expected"))
+    isempty(terms) && throw(ArgumentError("lincomb: one term at least (the identity alone has no context, element type or size)"))
+    hs, pairs = Ptr{Cvoid}[A.h for A in terms], lincomb_pairs(coefs, identity)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve terms check(ccall((:expv_mi_op_create_lincomb, lib), Cint, (Cint, Ptr{Ptr{Cvoid}}, Ptr{Cdouble}, Cint, Ref{Ptr{Cvoid}}),
+                                   length(hs), hs, pairs, identity === nothing ? Cint(0) : LINCOMB_IDENTITY, r), ctx().h)
+    C = wrap_operator(T, r[])
+    LINCOMB_KEPT[C] = (collect(terms), identity !== nothing)
+    C
+end
+function recombine!(C::MIOperator{T}, coefs, terms::Union{Nothing, AbstractVector{MIOperator{T}}} = nothing; identity = nothing) where {T}
+    haskey(LINCOMB_KEPT, C) || throw(ArgumentError("recombine!: only an operator made by lincomb (or by + - * /) recombines"))
+    kept, had = LINCOMB_KEPT[C]
+    had == (identity !== nothing) || throw(ArgumentError("recombine!: give `identity` exactly when the operator was made with one"))
+    terms === nothing && (terms = kept)      # the terms of the creation (or of the last recombine!)
+    length(coefs) == length(terms) || throw(DimensionMismatch("recombine!: one coefficient per term expected"))
+    hs, pairs = Ptr{Cvoid}[A.h for A in terms], lincomb_pairs(coefs, identity)
+    GC.@preserve terms check(ccall((:expv_mi_op_lincomb_refresh, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cdouble}),
+                                   C.h, length(hs), hs, pairs), ctx().h)
+    LINCOMB_KEPT[C] = (collect(terms), identity !== nothing)
+    n, nz, hm, on, dt = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Cdouble}(0), Ref{Cint}(0)
+    check(ccall((:expv_mi_op_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Cint}, Ref{Cdouble}, Ref{Cint}), C.h, n, nz, hm, on, dt), ctx().h)
+    C.herm = hm[] != 0
+    C.nnz = nz[]
+    C.opnorm_inf = on[]
+    C
+end
+Base.:+(A::MIOperator{T}, B::MIOperator{T}) where {T} = lincomb([A, B], (1, 1))
+Base.:-(A::MIOperator{T}, B::MIOperator{T}) where {T} = lincomb([A, B], (1, -1))
+Base.:-(A::MIOperator) = lincomb([A], (-1,))
+Base.:*(c::Number, A::MIOperator) = lincomb([A], (c,))
+Base.:*(A::MIOperator, c::Number) = lincomb([A], (c,))
+Base.:/(A::MIOperator, c::Number) = lincomb([A], (inv(c),))      # (the reciprocal is rounded first, then every entry multiplied)
+Base.:+(A::MIOperator, J::UniformScaling) = lincomb([A], (1,); identity = J.λ)
+Base.:-(A::MIOperator, J::UniformScaling) = lincomb([A], (1,); identity = -J.λ)
 # A lazy A' / transpose(A) of a host SparseMatrixCSC needs no device transposition: the parent's CSC arrays ARE the CSR arrays of
 # the transpose (columns sorted by row = rows sorted by column); the values are conjugated for an Adjoint.
 function MIOperator(A::Union{Adjoint{T, SparseMatrixCSC{T, Int64}}, Transpose{T, SparseMatrixCSC{T, Int64}}}) where {T <: MIScalar}
