@@ -143,6 +143,10 @@ PROTOTYPES = {
     "expv_mi_host_taylor_grid_plan": (_i, [_i64, _pd, _i, _pi64, _pd, _pi]),
     "expv_mi_host_taylor_theta": (_i, [_i, _i, _pd]),
     "expv_mi_host_taylor_params": (_i, [_i, _d, _pi, _pi64]),
+    "expv_mi_host_taylor_params_power": (_i, [_i, _d, _pd, _pi, _pi64, _pi]),
+    "expv_mi_host_normest_signs": (_i, [_i64, _i, _i64, _vp]),
+    "expv_mi_op_norm_power": (_i, [_vp, _vp, _i, _d, _d, _i, _pi64, _pd]),
+    "expv_mi_expv_taylor_power": (_i, [_vp, _vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, _i64, _pi64, _pd]),
     "expv_mi_timestep_opts_default": (None, [C.POINTER(TimestepOpts)]),
     "expv_mi_timestep_caches_create": (_i, [_vp, _i, _i64, _i, _i, _pvp]),
     "expv_mi_timestep_caches_destroy": (_i, [_vp]),

@@ -33,6 +33,7 @@ __all__ = [
     "exponential", "exponential_", "mul_", "phi", "phi_", "balance_", "host_gebal",
     "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_dia_pattern", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
     "expv_taylor", "expv_taylor_", "expv_taylor_block", "expv_taylor_block_", "expv_taylor_grid", "expv_taylor_grid_", "host_taylor_grid_plan", "phiv_taylor", "phiv_taylor_", "host_taylor_theta", "host_taylor_params",
+    "expv_taylor_power", "expv_taylor_power_", "host_taylor_params_power", "host_normest_signs",
 ]
 
 ExpvMIError = L.ExpvMIError
@@ -1151,6 +1152,32 @@ class MIOperator:
         element types also the bits).  ``A.T`` is an alias that builds a new operator at every access."""
         return self._adjoint(L.OP_TRANSPOSE)
 
+    _NORMEST_INFO = ("iterations", "applications", "host_reads", "index", "resamples", "exit", "temporary_adjoint", "adjoint_us")
+
+    def norm_power(self, p, ord=np.inf, shift=0.0, adjoint=None, return_info=False):
+        """A lower bound of ``||(A - shift I)^p||`` in the infinity norm (``ord=inf``) or the 1-norm (``ord=1``), 1 <= p <= 16, by the
+        deterministic block 1-norm estimator on the device (expv_mi_op_norm_power; Higham & Tisseur 2000, t = 2): 2 p operator
+        applications per column and iteration, at most five iterations, no power is formed.  ``adjoint``: an operator of ``A'``
+        (``A.adjoint()``); None: a Hermitian operator serves as its own, otherwise one is made for the call.  p = 1 with ``ord=inf`` is
+        the exact row-sum norm.  ``ord`` is ``np.inf`` or the integer 1; anything else is refused.  ``return_info``: also the dictionary kept in ``self.last_norm_info`` (iterations, applications,
+        host_reads, index, resamples, exit, temporary_adjoint, adjoint_us)."""
+        if isinstance(ord, (bool, np.bool_)):
+            which = -1
+        elif isinstance(ord, (float, np.floating)) and ord == np.inf:
+            which = 0
+        elif isinstance(ord, (int, np.integer)) and ord == 1:
+            which = 1
+        else:
+            which = -1      # (anything but inf and 1: refused by the library)
+        if adjoint is not None and not isinstance(adjoint, MIOperator):
+            raise TypeError("norm_power: adjoint must be an MIOperator (A.adjoint())")
+        sh = complex(shift)
+        info, est = (C.c_int64 * 8)(), C.c_double(0.0)
+        _check(L.load().expv_mi_op_norm_power(self._h, None if adjoint is None else adjoint._h, int(p), sh.real, sh.imag, which, info,
+                                              C.byref(est)), self.ctx._h)
+        self.last_norm_info = dict(zip(self._NORMEST_INFO, (int(v) for v in info)))
+        return (float(est.value), self.last_norm_info) if return_info else float(est.value)
+
     H = property(adjoint, doc="``adjoint()``: a new operator at every access (the scipy convention), not cached")
     T = property(transpose, doc="``transpose()``: a new operator at every access (the scipy convention), not cached")
 
@@ -1975,6 +2002,73 @@ def host_taylor_params(alpha, precision=0):
     m, s = C.c_int(0), C.c_int64(0)
     _check(L.load().expv_mi_host_taylor_params(int(precision), float(alpha), C.byref(m), C.byref(s)))
     return int(m.value), int(s.value)
+
+
+def host_taylor_params_power(alpha1, d, precision=0):
+    """(m*, s, p_used) of the reference's whole parameter search (expv_mi_host_taylor_params_power; host only): ``alpha1`` =
+    |t| opnorm(A - mu I, Inf), ``d`` = the eight values d_2 .. d_9, d_p = |t| ||(A - mu I)^p||^(1/p).  p_used = 0: the first branch."""
+    dd = np.ascontiguousarray(d, dtype=np.float64)
+    if dd.shape != (8,):
+        raise DimensionMismatch("host_taylor_params_power: d holds the eight values d_2 .. d_9")
+    m, s, pu = C.c_int(0), C.c_int64(0), C.c_int(0)
+    _check(L.load().expv_mi_host_taylor_params_power(int(precision), float(alpha1), dd.ctypes.data_as(C.POINTER(C.c_double)), C.byref(m),
+                                                     C.byref(s), C.byref(pu)))
+    return int(m.value), int(s.value), int(pu.value)
+
+
+def host_normest_signs(n, col, attempt):
+    """The +-1 signs (int8) the norm estimator draws for natural rows 0 .. n - 1 of column ``col`` at draw ``attempt``
+    (expv_mi_host_normest_signs; host only): what a restatement of ``MIOperator.norm_power`` is pinned to."""
+    out = np.empty(max(int(n), 0), dtype=np.int8)
+    _check(L.load().expv_mi_host_normest_signs(int(n), int(col), int(attempt), out.ctypes.data if out.size else None))
+    return out
+
+
+_TAYLOR_POWER_INFO = _TAYLOR_INFO + ("p_used", "normest_applications", "normest_reads", "temporary_adjoint")
+
+
+def expv_taylor_power_(w, t, A, b, *, adjoint=None, precision=None, max_matvecs=0, return_info=False, ctx=None):
+    """w <- exp(t A) b by the truncated Taylor series with the reference's WHOLE parameter search (expv_mi_expv_taylor_power): when
+    alpha = |t| opnorm(A - mu I, Inf) is above the cheap threshold, d_p = |t| ||(A - mu I)^p||^(1/p), p = 2 .. 9, are estimated on the
+    device (``MIOperator.norm_power``) and (m*, s) come from ``host_taylor_params_power`` -- orders of magnitude fewer operator
+    applications for a non-normal ``A``.  Below the threshold the call is ``expv_taylor_``, bit for bit.  ``adjoint``: an operator of
+    ``A'`` (``A.adjoint()``), or None: a Hermitian ``A`` serves as its own, otherwise one is made for the call.  Stored operators
+    only.  Everything else as ``expv_taylor_``; the info dictionary (``expv_taylor_power.last_info``) adds p_used,
+    normest_applications, normest_reads, temporary_adjoint and d (d_2 .. d_9)."""
+    tr, ti, _ = _t_parts(t)
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(b))
+    opT = _as_operator(op, T)
+    if adjoint is not None and not isinstance(adjoint, MIOperator):
+        raise TypeError("expv_taylor_power: adjoint must be an MIOperator (A.adjoint())")
+    ba, wa = _Arg(_host_view(b), T), _Arg(_host_view(w), T, writable=True)
+    n = opT.shape[0]
+    if int(np.prod(ba.shape)) != n:
+        raise DimensionMismatch(f"length(b) [{int(np.prod(ba.shape))}] == size(A,1) [{n}] doesn't hold")
+    if int(np.prod(wa.shape)) != n:
+        raise DimensionMismatch(f"length(w) [{int(np.prod(wa.shape))}] == size(A,1) [{n}] doesn't hold")
+    info, dinfo = (C.c_int64 * 12)(), (C.c_double * 12)()
+    _check(L.load().expv_mi_expv_taylor_power(opT.ctx._h, opT._h, None if adjoint is None else adjoint._h, tr, ti, ba.ptr, ba.loc, wa.ptr,
+                                              wa.loc, int(precision or 0), int(max_matvecs), info, dinfo), opT.ctx._h)
+    wa.finish()
+    d = dict(zip(_TAYLOR_POWER_INFO, (int(v) for v in info)))
+    d.update(alpha=float(dinfo[0]), mu=complex(dinfo[1], dinfo[2]) if T.kind == "c" else float(dinfo[1]), normF=float(dinfo[3]),
+             d=[float(v) for v in dinfo[4:12]])
+    expv_taylor_power.last_info = d
+    return (w, d) if return_info else w
+
+
+def expv_taylor_power(t, A, b, *, adjoint=None, precision=None, max_matvecs=0, return_info=False, ctx=None):
+    """exp(t A) b by the truncated Taylor series with the whole parameter search (see expv_taylor_power_): the result lives where
+    ``b`` does and has the element type the device worked in."""
+    op = _as_operator(A, None, ctx)
+    T = _work_dtype(op.dtype, _np_dtype_of(b))
+    if _is_torch(b) and not b.is_cuda:
+        import torch
+        w = torch.empty(b.shape[0], dtype=_torch_dtype(T))
+    else:
+        w = _empty_like(b, (b.shape[0],), T)
+    return expv_taylor_power_(w, t, op, b, adjoint=adjoint, precision=precision, max_matvecs=max_matvecs, return_info=return_info, ctx=ctx)
 
 
 def phiv_(w, t, Ks, k, *, correct=False, errest=False):

@@ -13,6 +13,7 @@
 #include <unordered_map>
 
 #include "engine.h"
+#include "mix64.h"
 #include "op_lincomb.h"
 #include "reorder.h"
 
@@ -3116,6 +3117,28 @@ int expv_mi_expv_error_estimate(expv_mi_ks_t ks, expv_mi_op_t op, double t_re, d
 }
 
 // ------------------------------------------------------------------ truncated Taylor series (expv_taylor.hip) ----
+// The tail of a single-vector Taylor entry (expv_mi_expv_taylor, expv_mi_expv_taylor_power): the result goes to the caller behind
+// the last launch -- through the inverse permutation of an operator stored as P A P' -- and shares the wait of the state read-back.
+static void taylor_deliver(Ctx *ctx, Op &op, TaylorCall &tc, void *w, int w_loc, int64_t *info, double *dinfo) {
+  const int64_t n = op.n;
+  const size_t esz = dtype_size(op.dtype), bytes = (size_t)n * esz;
+  DevBuf out;
+  try {
+    hipStream_t s = ctx->stream;
+    const void *src = tc.F;
+    if (op.perm) {      // rows back to their natural places
+      void *dst = w;
+      if (w_loc == EXPV_MI_HOST) { out.take_from(ctx, bytes + 16); dst = out.p; }
+      dev::gather_rows(s, esz, dst, n, tc.F, n, op.perm->pinv.as<int32_t>(), n, 1);
+      src = (w_loc == EXPV_MI_HOST) ? dst : nullptr;
+    }
+    if (src) HIPCHECK(hipMemcpyAsync(w, src, bytes, w_loc == EXPV_MI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+    taylor_collect(ctx, tc, info, dinfo);
+  } catch (...) {
+    (void)hipStreamSynchronize(ctx->stream);
+    throw;
+  }
+}
 int expv_mi_expv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc, void *w, int w_loc,
                         int precision, int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4]) {
   return guarded(ctx, [&] {
@@ -3128,27 +3151,12 @@ int expv_mi_expv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double 
     if (n == 0) return;
     if (!b || !w) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: null pointer");
     ctx->use();
-    const size_t esz = dtype_size(op->dtype), bytes = (size_t)n * esz;
-    DevBuf tmp, out;
+    const size_t esz = dtype_size(op->dtype);
+    DevBuf tmp;
     const void *bd = vector_in(ctx, *op, b, b_loc, n, esz, tmp);
     TaylorCall tc;
     taylor_enqueue(ctx, *op, t_re, t_im, bd, precision, max_matvecs, opnorm, tc);
-    try {
-      // the result goes to the caller behind the last launch and shares the wait of the state read-back
-      hipStream_t s = ctx->stream;
-      const void *src = tc.F;
-      if (op->perm) {      // stored as P A P': rows back to their natural places
-        void *dst = w;
-        if (w_loc == EXPV_MI_HOST) { out.take_from(ctx, bytes + 16); dst = out.p; }
-        dev::gather_rows(s, esz, dst, n, tc.F, n, op->perm->pinv.as<int32_t>(), n, 1);
-        src = (w_loc == EXPV_MI_HOST) ? dst : nullptr;
-      }
-      if (src) HIPCHECK(hipMemcpyAsync(w, src, bytes, w_loc == EXPV_MI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
-      taylor_collect(ctx, tc, info, dinfo);
-    } catch (...) {
-      (void)hipStreamSynchronize(ctx->stream);
-      throw;
-    }
+    taylor_deliver(ctx, *op, tc, w, w_loc, info, dinfo);
   });
 }
 int expv_mi_expv_taylor_block(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *B, int64_t ldb, int ncols,
@@ -3282,6 +3290,110 @@ int expv_mi_host_taylor_params(int precision, double alpha, int *m, int64_t *s) 
     taylor_params(precision, alpha, m, s);
   });
 }
+int expv_mi_host_taylor_params_power(int precision, double alpha1, const double d[8], int *m, int64_t *s, int *p_used) {
+  return guarded(nullptr, [&] {
+    if (!m || !s || !p_used) fail(EXPV_MI_ARGUMENT_ERROR, "host_taylor_params_power: null output");
+    if (!d) fail(EXPV_MI_ARGUMENT_ERROR, "host_taylor_params_power: null d");
+    taylor_params_power(precision, alpha1, d, m, s, p_used);
+  });
+}
+int expv_mi_host_normest_signs(int64_t n, int col, int64_t attempt, int8_t *out) {
+  return guarded(nullptr, [&] {
+    if (n < 0 || col < 0 || attempt < 0 || attempt > 0xffffffffll) fail(EXPV_MI_ARGUMENT_ERROR, "host_normest_signs: n, col and attempt must be non-negative");
+    if (n > 0 && !out) fail(EXPV_MI_ARGUMENT_ERROR, "host_normest_signs: null output");
+    normest_signs_host(n, col, attempt, out);
+  });
+}
+
+// ------------------------------------------------------------------ norm estimator (op_normest.hip) ----
+// The operator of A' for an estimator call: the caller's, A itself when it is Hermitian, or one made for the call and destroyed
+// with this object.
+struct AdjointForCall {
+  expv_mi_op_t adj = nullptr;
+  bool temp = false;
+  int64_t us = 0;
+  AdjointForCall(const char *who, expv_mi_op_t op, expv_mi_op_t given) {
+    const std::string w(who);
+    if (given) {
+      if (!given->ctx || given->ctx != op->ctx) fail(EXPV_MI_ARGUMENT_ERROR, w + ": adj lives on another context than op");
+      if (given->dtype != op->dtype || given->n != op->n) fail(EXPV_MI_ARGUMENT_ERROR, w + ": adj differs from op in dtype or n");
+      if (given->kind == OP_CALLBACK) fail(EXPV_MI_UNSUPPORTED, w + ": a matrix-free adjoint is not supported");
+      adj = given;
+    } else if (op->ishermitian) {
+      adj = op;
+    }
+  }
+  // the adjoint the call works with: made now when the caller gave none and A is not its own
+  void create(const std::string &w, expv_mi_op_t op) {
+    if (adj) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = expv_mi_op_create_adjoint(op, EXPV_MI_OP_ADJOINT, &adj);
+    if (rc != EXPV_MI_OK) fail(rc, w + ": " + op->ctx->last_error);
+    temp = true;
+    us = (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+  }
+  ~AdjointForCall() {
+    if (temp && adj) (void)expv_mi_op_destroy(adj);
+  }
+};
+
+int expv_mi_op_norm_power(expv_mi_op_t op, expv_mi_op_t adj, int p, double shift_re, double shift_im, int which, int64_t info[8],
+                          double *est) {
+  Ctx *ctx = op ? op->ctx : nullptr;
+  return guarded(ctx, [&] {
+    if (info) std::fill(info, info + 8, (int64_t)0);
+    if (!op || !ctx) fail(EXPV_MI_ARGUMENT_ERROR, "op_norm_power: null operator, or one whose context is gone");
+    if (!est) fail(EXPV_MI_ARGUMENT_ERROR, "op_norm_power: null output");
+    if (p < 1 || p > 16) fail(EXPV_MI_ARGUMENT_ERROR, "op_norm_power: p = " + std::to_string(p) + " is outside 1 .. 16");
+    if (which != 0 && which != 1) fail(EXPV_MI_ARGUMENT_ERROR, "op_norm_power: which must be 0 (infinity norm) or 1 (1-norm)");
+    if (op->kind == OP_CALLBACK) fail(EXPV_MI_UNSUPPORTED, "op_norm_power: a matrix-free operator has no adjoint to estimate with");
+    if (shift_im != 0.0 && !dtype_is_complex(op->dtype)) fail(EXPV_MI_ARGUMENT_ERROR, "op_norm_power: a complex shift needs a complex operator");
+    if (!std::isfinite(shift_re) || !std::isfinite(shift_im)) fail(EXPV_MI_ARGUMENT_ERROR, "op_norm_power: the shift is not finite");
+    AdjointForCall a("op_norm_power", op, adj);
+    int64_t ninfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (op->n == 0) {
+      *est = 0.0;
+    } else if (p == 1 && which == 0) {      // the exact row-sum norm
+      const bool f32 = dtype_is_32bit(op->dtype);      // sigma rounded to the element type, as the estimator's kernels take it
+      *est = taylor_rownorm(ctx, *op, f32 ? (double)(float)shift_re : shift_re, f32 ? (double)(float)shift_im : shift_im);
+      ninfo[2] = 1; ninfo[3] = -1; ninfo[5] = 7;
+    } else {
+      a.create("op_norm_power", op);
+      normest_run(ctx, *op, *a.adj, p, shift_re, shift_im, which, ninfo, est);
+    }
+    ninfo[6] = a.temp ? 1 : 0;
+    ninfo[7] = a.us;
+    if (info) std::copy(ninfo, ninfo + 8, info);
+  });
+}
+
+int expv_mi_expv_taylor_power(expv_mi_ctx_t ctx, expv_mi_op_t op, expv_mi_op_t adj, double t_re, double t_im, const void *b, int b_loc,
+                              void *w, int w_loc, int precision, int64_t max_matvecs, int64_t info[12], double dinfo[12]) {
+  return guarded(ctx, [&] {
+    if (info) std::fill(info, info + 12, (int64_t)0);
+    if (dinfo) std::fill(dinfo, dinfo + 12, 0.0);
+    if (!ctx || !op) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: null context / operator");
+    if ((b_loc != EXPV_MI_HOST && b_loc != EXPV_MI_DEVICE) || (w_loc != EXPV_MI_HOST && w_loc != EXPV_MI_DEVICE))
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: unknown loc");
+    if (op->kind == OP_CALLBACK) fail(EXPV_MI_UNSUPPORTED, "expv_taylor_power: a matrix-free operator has no adjoint to estimate with");
+    AdjointForCall a("expv_taylor_power", op, adj);
+    const int64_t n = op->n;
+    if (n == 0) return;
+    if (!b || !w) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: null pointer");
+    ctx->use();
+    const size_t esz = dtype_size(op->dtype);
+    DevBuf tmp;
+    const void *bd = vector_in(ctx, *op, b, b_loc, n, esz, tmp);
+    TaylorCall tc;
+    int64_t pinfo[3] = {0, 0, 0};
+    double d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // (a temporary adjoint is made only when the estimator runs: the plan's alpha decides)
+    taylor_power_enqueue(ctx, *op, [&]() -> Op & { a.create("expv_taylor_power", op); return *a.adj; }, t_re, t_im, bd, precision, max_matvecs, tc, pinfo, d);
+    taylor_deliver(ctx, *op, tc, w, w_loc, info, dinfo);
+    if (info) { info[8] = pinfo[0]; info[9] = pinfo[1]; info[10] = pinfo[2]; info[11] = a.temp ? 1 : 0; }
+    if (dinfo) std::copy(d, d + 8, dinfo + 4);
+  });
+}
 
 // ------------------------------------------------------------------ time stepping -----------
 void expv_mi_timestep_opts_default(expv_mi_timestep_opts *o) {
@@ -3366,11 +3478,7 @@ int expv_mi_kiops(expv_mi_ctx_t ctx, expv_mi_op_t op, const double *tau_out, int
 // words left that sum unchanged.  Here every word goes through a bijective non-linear mixer AFTER being combined with its
 // position, so a permutation of the contents changes the sum unless two 64-bit mixed values collide.  A sum mod 2^64 is
 // associative: the split over threads does not change the value.
-static inline uint64_t mix64(uint64_t h) {
-  h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-  return h;
-}
-static constexpr uint64_t kHashSalt = 0x9e3779b97f4a7c15ull;
+// (mix64 and kHashSalt: mix64.h, shared with the norm estimator)
 int expv_mi_host_wrapsum(const void *buf, uint64_t nbytes, uint64_t out[2]) {
   return guarded(nullptr, [&] {
     if ((!buf && nbytes) || !out) fail(EXPV_MI_ARGUMENT_ERROR, "wrapsum: bad arguments");

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -618,6 +619,20 @@ void taylor_run(Ctx *ctx, Op &op, double t_re, double t_im, const void *b_dev, v
 // operator's opnorm), and (m*, s), tol and the max_matvecs refusal for the alpha in tc -- with the messages of expv_taylor.
 void taylor_check(const Op &op, double t_im, int precision, double opnorm);
 void taylor_choose(const Op &op, int precision, int64_t max_matvecs, TaylorCall &tc);
+// The reference's whole parameter search (:99-121), host only: alpha_1 and d_2 .. d_9 in, (m*, s) and the winning p out (0: the
+// first branch); its cheap threshold; the exact ||A - sigma I||_inf of a stored operator (the plan's norm pass, one blocking read);
+// and expv_taylor with that search: as taylor_enqueue, adj() hands over the operator of A' when the estimator runs, pinfo = p_used, the estimator's panel applications and blocking reads.
+double taylor_power_threshold(int precision);
+void taylor_params_power(int precision, double alpha1, const double d[8], int *m, int64_t *s, int *p_used);
+double taylor_rownorm(Ctx *ctx, Op &op, double sigma_re, double sigma_im);
+void taylor_power_enqueue(Ctx *ctx, Op &op, const std::function<Op &()> &adj, double t_re, double t_im, const void *b_dev, int precision, int64_t max_matvecs,
+                          TaylorCall &tc, int64_t pinfo[3], double d[8]);
+
+// ---- op_normest.hip -----------------------------------------------------------------------
+// A lower bound of ||(A - sigma I)^p||_inf (which = 0) or _1 (which = 1) by the block 1-norm estimator (include/expv_mi.h:
+// expv_mi_op_norm_power); adj is the operator of A' (op itself for a Hermitian one); the arguments have been checked.  info[0..5].
+void normest_run(Ctx *ctx, Op &op, Op &adj, int p, double shift_re, double shift_im, int which, int64_t info[8], double *est);
+void normest_signs_host(int64_t n, int col, int64_t attempt, int8_t *out);
 
 // ---- expv_taylor_block.hip ------------------------------------------------------------------
 // exp(tA)B for an n x ncols block (include/expv_mi.h: expv_mi_expv_taylor_block); the arguments have been checked by the caller.

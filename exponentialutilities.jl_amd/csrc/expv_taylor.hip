@@ -17,7 +17,8 @@
 // Traffic per term: fused kernel (SELL slots without overflow, or the general diagonal form): the operator + x gather, x_i, F read,
 // y and F written -- the operator plus four vector streams.  Everything else: mul! (operator, x, y) + one update pass over x, y, F.
 //
-// This file holds the plan (mu, alpha, m*, s) and the host loop of the single call.  The term kernel k_taylor_term<T, FUSED>, its row
+// This file holds the plan (mu, alpha, m*, s), the reference's whole parameter search behind power norms (taylor_params_power; the norms
+// come from op_normest.hip) and the host loop of the single call.  The term kernel k_taylor_term<T, FUSED>, its row
 // sweep and the launch setup shared with the phiv and grid entries are in taylor_term.h; the stage state, the closing kernel and the
 // element step that fixes the roundings of a term are in taylor_state.h.
 #include <cmath>
@@ -134,6 +135,47 @@ void taylor_params(int precision, double alpha, int *m_out, int64_t *s_out) {
   *s_out = (int64_t)best_s;
 }
 
+// The whole search (:99-121), given alpha_1 and d[i] = ||B^(i+2)||^(1/(i+2)), i = 0 .. 7 (d_2 .. d_9, |t| folded in).  Below the cheap
+// threshold 4 theta_55 P (P + 3) / 55, P = 8, the first branch; otherwise for p = 2 .. 8 alpha_p = max(d_p, d_{p+1}) and the first
+// minimum of m ceil(alpha_p / theta_m) over p (p - 1) - 1 <= m <= 55; the overall minimum by (cost, m), the first p that reaches it;
+// s = max(cost / m, 1).  A candidate whose stage count is beyond every 64-bit count is skipped, as in taylor_params.
+double taylor_power_threshold(int precision) {
+  return 4.0 * taylor_table(precision)[TAYLOR_M_MAX - 1] * 8.0 * 11.0 / 55.0;
+}
+void taylor_params_power(int precision, double alpha1, const double d[8], int *m_out, int64_t *s_out, int *p_used) {
+  const double *th = taylor_table(precision);
+  if (!(alpha1 >= 0.0) || !std::isfinite(alpha1))
+    fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: alpha = |t| opnorm(A - mu I, Inf) = " + std::to_string(alpha1) + " is not a finite non-negative number");
+  *p_used = 0;
+  if (alpha1 == 0.0) { *m_out = 0; *s_out = 1; return; }
+  if (alpha1 <= taylor_power_threshold(precision)) { taylor_params(precision, alpha1, m_out, s_out); return; }
+  for (int i = 0; i < 8; ++i)
+    if (!(d[i] >= 0.0) || !std::isfinite(d[i]))
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: d_" + std::to_string(i + 2) + " = " + std::to_string(d[i]) + " is not a finite non-negative number");
+  bool have = false;
+  unsigned __int128 best_cost = 0;
+  int best_m = 1, best_p = 0;
+  for (int p = 2; p <= 8; ++p) {
+    const double ap = std::max(d[p - 2], d[p - 1]);
+    bool have_p = false;
+    unsigned __int128 cost_p = 0;
+    int m_p = 0;
+    for (int m = p * (p - 1) - 1; m <= TAYLOR_M_MAX; ++m) {
+      const double sd = std::ceil(ap / th[m - 1]);
+      if (!(sd < 0x1p100)) continue;
+      const unsigned __int128 cost = (unsigned __int128)sd * (unsigned)m;
+      if (!have_p || cost < cost_p) { have_p = true; cost_p = cost; m_p = m; }
+    }
+    if (have_p && (!have || cost_p < best_cost || (cost_p == best_cost && m_p < best_m))) { have = true; best_cost = cost_p; best_m = m_p; best_p = p; }
+  }
+  const unsigned __int128 sq = have ? best_cost / (unsigned)best_m : 0;
+  if (!have || !(sq < ((unsigned __int128)1 << 62)))
+    fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: alpha = " + std::to_string(alpha1) + " needs more stages than a 64-bit count holds");
+  *m_out = best_m;
+  *s_out = std::max<int64_t>((int64_t)sq, 1);
+  *p_used = best_p;
+}
+
 // ------------------------------------------------------------------------------------------
 // the call
 // ------------------------------------------------------------------------------------------
@@ -248,6 +290,79 @@ void taylor_enqueue(Ctx *c, Op &op, double t_re, double t_im, const void *b_dev,
     taylor_run(c, op, t_re, t_im, b_dev, base, base + head, base + head + vbytes, tc.F, tc);
   } catch (...) {
     (void)hipStreamSynchronize(c->stream);      // (the work vectors go back to the context: nothing may still be writing them)
+    throw;
+  }
+}
+
+// ||A - sigma I||_inf of a stored operator, exactly: the norm pass of the plan with sigma in the place of mu (one blocking read)
+double taylor_rownorm(Ctx *c, Op &op, double sigma_re, double sigma_im) {
+  c->use();
+  DevBuf head;
+  head.take_from(c, taylor_head_bytes());
+  dev::TaylorState h;
+  try {
+    dispatch_dtype(op.dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipStream_t s = c->stream;
+      dev::TaylorState *st = head.as<dev::TaylorState>();
+      std::memset(&h, 0, sizeof(h));
+      std::memcpy(&h.mu_re, &sigma_re, 8);
+      std::memcpy(&h.mu_im, &sigma_im, 8);
+      HIPCHECK(hipMemcpyAsync(st, &h, sizeof(h), hipMemcpyHostToDevice, s));
+      const bool dense = op.kind == OP_DENSE;
+      if (!dense && !(op.rowptr.p && (op.nnz == 0 || (op.col.p && op.val.p)))) fail(EXPV_MI_ARGUMENT_ERROR, "op_norm_power: sparse operator without its CSR arrays");
+      {
+        ProfScope ps(c, EXPV_MI_K_LINCOMB);
+        hipLaunchKernelGGL(dev::k_taylor_shift_norm<T>, dim3(dev::taylor_grid(op.n, dev::BLOCK)), dim3(dev::BLOCK), 0, s, 1, op.n,
+                           dense ? nullptr : op.rowptr.as<int32_t>(), dense ? nullptr : op.col.as<int32_t>(),
+                           dense ? reinterpret_cast<const T *>(op.dense_ptr) : op.val.as<T>(), dense ? op.lda : (int64_t)0,
+                           reinterpret_cast<double *>(head.as<char>() + sizeof(dev::TaylorState)), st);
+      }
+      HIPCHECK(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipStreamSynchronize(s));
+    });
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
+    throw;
+  }
+  return (h.nanflags & 4ull) ? std::numeric_limits<double>::quiet_NaN() : f64_of(h.rowmax);
+}
+
+// expv_taylor with the whole parameter search: the plan of taylor_enqueue, then -- above the cheap threshold -- d_2 .. d_9 of
+// B = A - mu I from the norm estimator and (m*, s) from taylor_params_power, then the unchanged series.  pinfo: p_used, the
+// estimator's panel applications, its blocking reads; d[8]: d_2 .. d_9 (zeros when nothing was estimated).
+void taylor_power_enqueue(Ctx *c, Op &op, const std::function<Op &()> &get_adj, double t_re, double t_im, const void *b_dev, int precision, int64_t max_matvecs,
+                          TaylorCall &tc, int64_t pinfo[3], double d[8]) {
+  c->use();
+  try {
+    const size_t vbytes = up16((size_t)op.n * dtype_size(op.dtype)) + 16, head = taylor_head_bytes();
+    tc.work.take_from(c, head + 3 * vbytes);
+    char *base = tc.work.as<char>();
+    tc.state = base;
+    tc.F = base + head + 2 * vbytes;
+    taylor_shift_plan(c, op, t_re, t_im, precision, 0, 0.0, base, tc);      // (the refusal waits for the refined parameters)
+    const int table = (precision == 1 || dtype_is_32bit(op.dtype)) ? 1 : 0;
+    if (tc.alpha != 0.0 && tc.alpha > taylor_power_threshold(table)) {
+      const double at = std::hypot(t_re, t_im);
+      Op &adj = get_adj();
+      for (int p = 2; p <= 9; ++p) {
+        int64_t ninfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        double est = 0.0;
+        normest_run(c, op, adj, p, tc.mu_re, tc.mu_im, 0, ninfo, &est);
+        d[p - 2] = at * std::pow(est, 1.0 / (double)p);
+        pinfo[1] += ninfo[1];
+        pinfo[2] += ninfo[2];
+      }
+      int p_used = 0;
+      taylor_params_power(table, tc.alpha, d, &tc.m, &tc.s, &p_used);
+      pinfo[0] = p_used;
+    }
+    if (max_matvecs > 0 && (unsigned __int128)tc.s * (unsigned)tc.m > (unsigned __int128)max_matvecs)
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor: alpha = " + std::to_string(tc.alpha) + " needs m* = " + std::to_string(tc.m) + " terms in each of s = " +
+                                       std::to_string(tc.s) + " stages, more than max_matvecs = " + std::to_string(max_matvecs));
+    taylor_run(c, op, t_re, t_im, b_dev, base, base + head, base + head + vbytes, tc.F, tc);
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);
     throw;
   }
 }

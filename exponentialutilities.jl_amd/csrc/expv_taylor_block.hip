@@ -50,35 +50,7 @@ struct TaylorBlockState {
 };
 static_assert(sizeof(TaylorBlockState) == 512, "TaylorBlockState layout");
 
-// one row of an interleaved work vector: the P values of a row, adjacent and 16-byte aligned
-template <class T, int P>
-struct __attribute__((aligned(16))) RowP {
-  static_assert(P * sizeof(T) % 16 == 0, "a row of the interleaved work vectors is a whole number of 16-byte packs");
-  T v[P];
-};
-
-// the right-hand side of the operator loops of sparse_rows.h: P columns at once
-template <class T, int P>
-struct BlockColumns {
-  using row_t = RowP<T, P>;
-  const T *__restrict__ x;
-  T (*acc)[P];
-  __device__ __forceinline__ void clear(int k) {
-#pragma unroll
-    for (int p = 0; p < P; ++p) acc[k][p] = ST<T>::zero();
-  }
-  __device__ __forceinline__ row_t at(int64_t c) const { return *reinterpret_cast<const row_t *>(x + c * P); }
-  __device__ __forceinline__ static row_t none() {
-    row_t r;
-#pragma unroll
-    for (int p = 0; p < P; ++p) r.v[p] = ST<T>::zero();
-    return r;
-  }
-  __device__ __forceinline__ void fma(int k, T a, const row_t &g) {
-#pragma unroll
-    for (int p = 0; p < P; ++p) ST<T>::fma_(acc[k][p], a, g.v[p]);
-  }
-};
+// (RowP, one row of an interleaved work vector, and BlockColumns, the right-hand side of the operator loops for P columns: sparse_rows.h)
 
 // taylor_arrive for P columns: this workgroup's maxima into the panel's state, then one ticket
 template <int P>

@@ -1,6 +1,7 @@
 // sparse_rows.h -- the rows of a stored sparse operator applied to a vector, one 16-byte row pack per lane (gfx950 only):
 // from the SELL-C slots or from the general DIA form.  Shared by the Krylov half-steps (fused.hip) and the truncated-Taylor term
-// kernels (expv_taylor.hip: one vector; expv_taylor_block.hip: P interleaved columns behind the same two loops).
+// kernels (expv_taylor.hip: one vector; expv_taylor_block.hip and the norm estimator's panel kernel, op_normest.hip: P interleaved
+// columns behind the same two loops).
 #pragma once
 #include "kernel_common.h"
 
@@ -49,6 +50,36 @@ struct OneVector {
   __device__ __forceinline__ T at(int64_t c) const { return x[c]; }
   __device__ __forceinline__ static T none() { return ST<T>::zero(); }
   __device__ __forceinline__ void fma(int k, T a, const T &g) { ST<T>::fma_(acc[k], a, g); }
+};
+
+// one row of an interleaved work vector: the P values of a row, adjacent and 16-byte aligned
+template <class T, int P>
+struct __attribute__((aligned(16))) RowP {
+  static_assert(P * sizeof(T) % 16 == 0, "a row of the interleaved work vectors is a whole number of 16-byte packs");
+  T v[P];
+};
+
+// the right-hand side of the operator loops of sparse_rows.h: P columns at once
+template <class T, int P>
+struct BlockColumns {
+  using row_t = RowP<T, P>;
+  const T *__restrict__ x;
+  T (*acc)[P];
+  __device__ __forceinline__ void clear(int k) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) acc[k][p] = ST<T>::zero();
+  }
+  __device__ __forceinline__ row_t at(int64_t c) const { return *reinterpret_cast<const row_t *>(x + c * P); }
+  __device__ __forceinline__ static row_t none() {
+    row_t r;
+#pragma unroll
+    for (int p = 0; p < P; ++p) r.v[p] = ST<T>::zero();
+    return r;
+  }
+  __device__ __forceinline__ void fma(int k, T a, const row_t &g) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) ST<T>::fma_(acc[k][p], a, g.v[p]);
+  }
 };
 
 // y-rows of one slice for this lane from the DIA form: acc[k] = sum_d val[d][r] * x[r + off[d]]  (ascending offsets =

@@ -638,8 +638,8 @@ int expv_mi_expv_error_estimate(expv_mi_ks_t ks, expv_mi_op_t op, double t_re, d
  *     In SINGLE arithmetic the series loses accuracy through its hump: the rounding error is about eps32 e^(alpha / s), and the
  *     2^-24 table allows alpha / s up to 13.4 (-i Laplacian, ComplexF32, alpha / s = 10: 3e-4; typical cases 2e-7 .. 6e-7).  That is
  *     the reference's behaviour for Float32 and is kept: no cap on alpha / s.
- *   - Only the first branch of the reference's parameter search is built (alpha for every p: valid, conservative); the power-norm
- *     refinement needs products with A'.  max_matvecs > 0 and m* s > max_matvecs: EXPV_MI_ARGUMENT_ERROR naming alpha, m*, s;
+ *   - This entry takes the first branch of the reference's parameter search (alpha for every p: valid, conservative); the power-norm
+ *     refinement, which needs products with A', is expv_mi_expv_taylor_power.  max_matvecs > 0 and m* s > max_matvecs: EXPV_MI_ARGUMENT_ERROR naming alpha, m*, s;
  *     nothing is computed, w is untouched.  A non-finite alpha is an EXPV_MI_ARGUMENT_ERROR too.
  *   - The stopping rule is decided on the device: the host enqueues s (m* + 1) launches and reads nothing in between; the launches
  *     of a stopped stage return at once.  The maxima are order-independent: the same inputs give the same bits.
@@ -658,6 +658,60 @@ int expv_mi_host_taylor_theta(int precision, int m, double *theta);
 /* Host only: m* = argmin over 1 <= m <= 55 of m ceil(alpha / theta_m) (the first minimum on ties), s = ceil(alpha / theta_m*);
  * alpha = 0 gives (0, 1); a negative, NaN or infinite alpha EXPV_MI_ARGUMENT_ERROR (message: expv_mi_last_error(NULL)). */
 int expv_mi_host_taylor_params(int precision, double alpha, int *m, int64_t *s);
+/* Host only: the reference's WHOLE parameter search (ext/ExponentialUtilitiesStaticArraysExt.jl:99-121).  alpha1 = |t| opnorm(B, Inf),
+ * d[i] = |t| ||B^(i+2)||^(1/(i+2)), i = 0 .. 7 (d_2 .. d_9), B = A - mu I.  alpha1 = 0 gives (0, 1).  alpha1 <= 4 theta_55 * 8 * 11 / 55
+ * (the cheap condition): the result of expv_mi_host_taylor_params, p_used = 0, d is not read.  Otherwise, for p = 2 .. 8,
+ * alpha_p = max(d_p, d_{p+1}) and the first minimum of m ceil(alpha_p / theta_m) over p (p - 1) - 1 <= m <= 55; the overall minimum
+ * is taken by (cost, m), p_used is the first p that reaches it, s = max(cost / m, 1) -- d all zero gives (1, 1).  Argument errors are
+ * those of expv_mi_host_taylor_params, and a d_p that is negative or not finite. */
+int expv_mi_host_taylor_params_power(int precision, double alpha1, const double d[8], int *m, int64_t *s, int *p_used);
+
+/* A lower bound of ||(A - sigma I)^p||_inf (which = 0) or ||(A - sigma I)^p||_1 (which = 1), 1 <= p <= 16, of a STORED operator,
+ * sparse or dense, all four element types, without forming a power: the block 1-norm estimator of Higham & Tisseur (SIAM J. Matrix
+ * Anal. Appl. 21, 2000, Algorithm 2.4) with t = 2 columns and itmax = 5 -- the "1-norm estimation algorithm" for want of which
+ * the reference's Taylor expv stops at N <= 50 (ext/ExponentialUtilitiesStaticArraysExt.jl:92-97).  An estimate never exceeds the
+ * norm (rounding apart) and is usually exact or within a few per cent.  sigma = shift_re + i shift_im (shift_im != 0 needs a
+ * complex operator).
+ *   - adj: an operator of A' on the same context with the same dtype and n (expv_mi_op_create_adjoint makes one).  NULL: A itself
+ *     when expv_mi_op_info reports it Hermitian; otherwise an adjoint is created for the call and destroyed (info[6], info[7]).
+ *     The infinity norm of B^p is the 1-norm of (B')^p: `which` only swaps the roles of op and adj and conjugates the shift.
+ *   - p = 1 with which = 0 is the EXACT row-sum norm, from the norm pass of expv_mi_expv_taylor; n <= 2 is exact too.
+ *   - Nothing is random and two calls give the same bits.  The start block is (1/n, +-1/n); every "random" sign is
+ *     expv_mi_host_normest_signs(natural row, column, draw), draws counted from 0 through the call; every tie (the larger column
+ *     sum, the 12 largest h_i, "h_max is h[ind_best]" -- an index comparison) goes to the smaller natural index; a column is
+ *     parallel to another when ALL n signs agree (integer counts); column sums are accumulated in fp64, per-workgroup partials
+ *     finished in index order.  Complex types take sign = y / |y| (0 -> 1) and no parallel tests.  Vectors cross between the two
+ *     operators in the natural ordering, so a reordered operator and its unreordered twin differ by rounding only.
+ *   - No overflow, no underflow: every application multiplies its result by the exact power of two that brings its INPUT column
+ *     to [1, 2) (complex: max(|re|, |im|)), the exponents are summed in integers and est is a double: est of 2^k A is 2^(kp) est of A,
+ *     the same mantissa.  The scale is applied to the result of an application, so inside one the accumulator holds two
+ *     applications' growth: this holds for ||A - sigma I|| between about 1e-19 and 1e19 in the 32-bit types (2^-511 .. 2^511 in the
+ *     64-bit ones).
+ *   - sigma is rounded to the operator's element type, for every p.
+ *   - Checks before any device work, EXPV_MI_ARGUMENT_ERROR "op_norm_power: ...": null op / est, p outside 1 .. 16, unknown which, a
+ *     matrix-free operator (EXPV_MI_UNSUPPORTED), a complex shift on a real operator, adj of another context, dtype or n.
+ * info (may be NULL): [0] iterations, [1] panel applications (one = the operator applied to both columns), [2] blocking reads (two
+ * per iteration, plus one per resampled column), [3] natural index of the column that gave est (-1: none), [4] resampled columns,
+ * [5] the exit: 1 est did not grow, 2 itmax, 3 every new sign column parallel to an old one, 4 h_max is the best index, 5 the most
+ * promising indices were visited already, 6 non-finite, 7 exact, [6] 1 = a temporary adjoint was made, [7] its cost in microseconds. */
+int expv_mi_op_norm_power(expv_mi_op_t op, expv_mi_op_t adj, int p, double shift_re, double shift_im, int which, int64_t info[8],
+                          double *est);
+/* Host only: out[i] = +1 or -1, i < n: the estimator's sign for natural row i of column `col` at draw `attempt` -- the low bit of
+ * the mixer behind expv_mi_host_wrapsum applied to ((i + 1) g) ^ (col << 32 | attempt). */
+int expv_mi_host_normest_signs(int64_t n, int col, int64_t attempt, int8_t *out);
+
+/* expv_mi_expv_taylor with the reference's whole parameter search.  mu and alpha1 as there.  alpha1 = 0 or the cheap condition of
+ * expv_mi_host_taylor_params_power: nothing is estimated and the call IS expv_mi_expv_taylor, bit for bit.  Otherwise d_2 .. d_9 =
+ * |t| est_p^(1/p), est_p = expv_mi_op_norm_power(op, adj, p, mu, which = 0), and (m*, s) = expv_mi_host_taylor_params_power(alpha1,
+ * d); the series, its stopping rule and every rounding are those of expv_mi_expv_taylor.  An estimate is a lower bound, so the
+ * search may choose fewer terms than exact norms would: the published algorithm's behaviour, kept.  For a non-normal operator
+ * (block-triangular couplings, the augmented matrix of a forced problem) m* s drops by orders of magnitude.  Stored operators only
+ * (matrix-free: EXPV_MI_UNSUPPORTED); adj as for expv_mi_op_norm_power, a temporary one is made only when the estimator runs;
+ * max_matvecs is compared with the refined m* s.  info (may be NULL): [0..7] as expv_mi_expv_taylor, [8] p_used, [9] the estimator's
+ * panel applications, [10] its blocking reads, [11] 1 = a temporary adjoint was made.  dinfo (may be NULL): [0..3] as
+ * expv_mi_expv_taylor, [4..11] d_2 .. d_9 (zeros when nothing was estimated). */
+int expv_mi_expv_taylor_power(expv_mi_ctx_t ctx, expv_mi_op_t op, expv_mi_op_t adj, double t_re, double t_im, const void *b, int b_loc,
+                              void *w, int w_loc, int precision, int64_t max_matvecs, int64_t info[12], double dinfo[12]);
 
 /* W = exp(t A) B for an n x ncols block B: ncols independent problems of expv_mi_expv_taylor that share every pass over the operator.
  * (mu, alpha, m*, s) depend on A and t alone and are computed once; every column keeps its own stopping state, and COLUMN k OF W IS BIT

@@ -780,6 +780,28 @@ function expv_taylor!(w::MIVector{T}, t::Number, A::MIOperator{T}, b::MIVector{T
     w
 end
 expv_taylor(t::Number, A::MIOperator{T}, b::MIVector{T}; kw...) where {T} = expv_taylor!(similar(b, T, (length(b),)), t, A, b; kw...)
+# The same with the reference's WHOLE parameter search (:99-121): above the cheap threshold d_p = |t| ||(A - mu I)^p||^(1/p), p = 2 .. 9,
+# are estimated on the device (opnorm_power) -- far fewer applications for a non-normal A; below it the call is expv_taylor!, bit
+# for bit.  adjoint: an operator of A' (nothing: a Hermitian A serves as its own, otherwise one is made for the call).
+function expv_taylor_power!(w::MIVector{T}, t::Number, A::MIOperator{T}, b::MIVector{T}; adjoint = nothing, precision::Integer = 0,
+                            max_matvecs::Integer = 0) where {T}
+    length(w) == length(b) == size(A, 1) || throw(DimensionMismatch("length(w), length(b) and size(A, 1) must agree"))
+    check(ccall((:expv_mi_expv_taylor_power, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Int64, Ptr{Int64}, Ptr{Cdouble}),
+                ctx().h, A.h, adjoint === nothing ? C_NULL : adjoint.h, real(t), imag(t), b.ptr, DEVICE, w.ptr, DEVICE, precision, max_matvecs,
+                C_NULL, C_NULL), ctx().h)
+    w
+end
+expv_taylor_power(t::Number, A::MIOperator{T}, b::MIVector{T}; kw...) where {T} = expv_taylor_power!(similar(b, T, (length(b),)), t, A, b; kw...)
+# A lower bound of opnorm((A - shift I)^p, q), q = Inf or 1, 1 <= p <= 16, by the deterministic block 1-norm estimator on the device
+# (Higham & Tisseur 2000, t = 2); p = 1 with q = Inf is the exact row-sum norm.
+function opnorm_power(A::MIOperator{T}, p::Integer, q::Real = Inf; shift::Number = 0.0, adjoint = nothing) where {T}
+    q == Inf || q == 1 || throw(ArgumentError("opnorm_power: q must be Inf or 1"))
+    est = Ref{Cdouble}(0.0)
+    check(ccall((:expv_mi_op_norm_power, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cint, Ptr{Int64}, Ptr{Cdouble}),
+                A.h, adjoint === nothing ? C_NULL : adjoint.h, p, Float64(real(shift)), Float64(imag(shift)), q == 1 ? 1 : 0, C_NULL, est), ctx().h)
+    est[]
+end
 # A block of columns: size(B, 2) independent problems that share every pass over the operator; W[:, k] is bit for bit
 # expv_taylor(t, A, B[:, k]).  W may be B.  A column that has stopped is masked but streamed until its panel of 8 has stopped.
 function expv_taylor!(W::MIMatrix{T}, t::Number, A::MIOperator{T}, B::MIMatrix{T}; precision::Integer = 0, max_matvecs::Integer = 0,
