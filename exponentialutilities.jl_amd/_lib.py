@@ -137,6 +137,7 @@ PROTOTYPES = {
     "expv_mi_expv": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, C.POINTER(ArnoldiOpts), C.POINTER(ExpvStats)]),
     "expv_mi_expv_error_estimate": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _d, _d, _i, _i]),
     "expv_mi_expv_taylor": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, _i64, _d, _pi64, _pd]),
+    "expv_mi_expv_taylor_realop": (_i, [_vp, _vp, _d, _d, _vp, _i, _i, _vp, _i, _i, _i64, _d, _pi64, _pd]),
     "expv_mi_expv_taylor_block": (_i, [_vp, _vp, _d, _d, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i, _i, _i64, _d, _pi64, _pd, _pi64, _pd]),
     "expv_mi_phiv_taylor": (_i, [_vp, _vp, _d, _d, _vp, _i64, _i, _i, _i, _vp, _i, _i, _i64, _d, _pi64, _pd]),
     "expv_mi_expv_taylor_grid": (_i, [_vp, _vp, _d, _d, _pd, _i, _vp, _i, _vp, _i64, _i, _i, _i, _i64, _d, _pi64, _pd, _pi64]),

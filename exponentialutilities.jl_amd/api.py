@@ -33,6 +33,7 @@ __all__ = [
     "exponential", "exponential_", "mul_", "phi", "phi_", "balance_", "host_gebal",
     "host_phiv_dense", "host_symtridiag_expcol", "host_symtridiag_exp_last", "host_pattern_info", "host_dia_pattern", "host_rcm", "host_patch_order", "clear_operator_cache", "plan_cache",
     "expv_taylor", "expv_taylor_", "expv_taylor_block", "expv_taylor_block_", "expv_taylor_grid", "expv_taylor_grid_", "host_taylor_grid_plan", "phiv_taylor", "phiv_taylor_", "host_taylor_theta", "host_taylor_params",
+    "expv_taylor_realop", "expv_taylor_realop_",
     "expv_taylor_power", "expv_taylor_power_", "host_taylor_params_power", "host_normest_signs",
 ]
 
@@ -1714,6 +1715,50 @@ def expv_taylor(t, A, b, *, precision=None, max_matvecs=0, opnorm=None, return_i
     else:
         w = _empty_like(b, (b.shape[0],), T)
     return expv_taylor_(w, t, op, b, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
+
+
+def expv_taylor_realop_(w, t, A, b, *, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """w <- exp(t A) b for a REAL operator, a complex (or real) ``t`` and complex vectors (expv_mi_expv_taylor_realop): the
+    Schroedinger / wave propagation exp(-i t H) b with a real sparse H.  The operator is used as it is stored -- no promoted complex
+    copy -- and the series, its plan and its roundings are those of expv_taylor_ (on an operator with a fused form the values are
+    those of expv_taylor on the promoted operator, element for element).  ``A``: anything real an API call takes as an operator
+    (a complex one is refused: ArgumentError naming expv_mi_expv_taylor).  ``b``: real or complex, numpy / torch (either side) /
+    DeviceArray, converted to the operator's precision; a real ``b`` is widened on the device.  ``w``: complex, of the operator's
+    precision; it may be ``b`` itself when ``b`` is complex.  The other arguments and the dictionary kept in
+    ``expv_taylor_realop.last_info`` are those of expv_taylor_ (path 2 applies the operator twice per term: to the real and to the
+    imaginary plane)."""
+    tr, ti, _ = _t_parts(t)
+    op = _as_operator(A, None, ctx)
+    Cd = _complex_of(op.dtype)
+    bdt = _np_dtype_of(b)
+    ba = _Arg(_host_view(b), Cd if (bdt.kind == "c" or np.dtype(op.dtype).kind == "c") else _real_of(op.dtype))
+    wa = _Arg(_host_view(w), Cd, writable=True)
+    n = op.shape[0]
+    if int(np.prod(ba.shape)) != n:
+        raise DimensionMismatch(f"length(b) [{int(np.prod(ba.shape))}] == size(A,1) [{n}] doesn't hold")
+    if int(np.prod(wa.shape)) != n:
+        raise DimensionMismatch(f"length(w) [{int(np.prod(wa.shape))}] == size(A,1) [{n}] doesn't hold")
+    info, dinfo = (C.c_int64 * 8)(), (C.c_double * 4)()
+    _check(L.load().expv_mi_expv_taylor_realop(op.ctx._h, op._h, tr, ti, ba.ptr, ba.loc, _code(ba.dtype), wa.ptr, wa.loc, int(precision or 0),
+                                               int(max_matvecs), 0.0 if opnorm is None else float(opnorm), info, dinfo), op.ctx._h)
+    wa.finish()
+    d = dict(zip(_TAYLOR_INFO, (int(v) for v in info)))
+    d.update(alpha=float(dinfo[0]), mu=float(dinfo[1]), normF=float(dinfo[3]))
+    expv_taylor_realop.last_info = d
+    return (w, d) if return_info else w
+
+
+def expv_taylor_realop(t, A, b, *, precision=None, max_matvecs=0, opnorm=None, return_info=False, ctx=None):
+    """exp(t A) b for a real operator with a complex time and / or a complex vector (see expv_taylor_realop_): the result is complex,
+    of the operator's precision, and lives where ``b`` does."""
+    op = _as_operator(A, None, ctx)
+    Cd = _complex_of(op.dtype)
+    if _is_torch(b) and not b.is_cuda:
+        import torch
+        w = torch.empty(b.shape[0], dtype=_torch_dtype(Cd))
+    else:
+        w = _empty_like(b, (b.shape[0],), Cd)
+    return expv_taylor_realop_(w, t, op, b, precision=precision, max_matvecs=max_matvecs, opnorm=opnorm, return_info=return_info, ctx=ctx)
 
 
 _TAYLOR_BLOCK_INFO = ("m", "s", "applications_total", "worked_launches", "launches", "host_reads", "path", "nonfinite_columns")

@@ -3119,9 +3119,11 @@ int expv_mi_expv_error_estimate(expv_mi_ks_t ks, expv_mi_op_t op, double t_re, d
 // ------------------------------------------------------------------ truncated Taylor series (expv_taylor.hip) ----
 // The tail of a single-vector Taylor entry (expv_mi_expv_taylor, expv_mi_expv_taylor_power): the result goes to the caller behind
 // the last launch -- through the inverse permutation of an operator stored as P A P' -- and shares the wait of the state read-back.
-static void taylor_deliver(Ctx *ctx, Op &op, TaylorCall &tc, void *w, int w_loc, int64_t *info, double *dinfo) {
+// esz: the element size of the result (0: the operator's; expv_mi_expv_taylor_realop returns the complex counterpart).
+static void taylor_deliver(Ctx *ctx, Op &op, TaylorCall &tc, void *w, int w_loc, int64_t *info, double *dinfo, size_t esz = 0) {
   const int64_t n = op.n;
-  const size_t esz = dtype_size(op.dtype), bytes = (size_t)n * esz;
+  if (esz == 0) esz = dtype_size(op.dtype);
+  const size_t bytes = (size_t)n * esz;
   DevBuf out;
   try {
     hipStream_t s = ctx->stream;
@@ -3157,6 +3159,39 @@ int expv_mi_expv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double 
     TaylorCall tc;
     taylor_enqueue(ctx, *op, t_re, t_im, bd, precision, max_matvecs, opnorm, tc);
     taylor_deliver(ctx, *op, tc, w, w_loc, info, dinfo);
+  });
+}
+int expv_mi_expv_taylor_realop(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc, int b_dtype, void *w,
+                               int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4]) {
+  return guarded(ctx, [&] {
+    if (info) std::fill(info, info + 8, (int64_t)0);
+    if (dinfo) std::fill(dinfo, dinfo + 4, 0.0);
+    if (!ctx || !op) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_realop: null context / operator");
+    if (dtype_is_complex(op->dtype))
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_realop: the operator is complex; expv_mi_expv_taylor is the call for a complex operator");
+    const int cdt = dtype_complex_of(op->dtype);
+    if (b_dtype != cdt && b_dtype != op->dtype)
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_realop: b_dtype = " + std::to_string(b_dtype) + " is neither the operator's real type (" +
+                                       std::to_string(op->dtype) + ") nor its complex type (" + std::to_string(cdt) + ")");
+    if ((b_loc != EXPV_MI_HOST && b_loc != EXPV_MI_DEVICE) || (w_loc != EXPV_MI_HOST && w_loc != EXPV_MI_DEVICE))
+      fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_realop: unknown loc");
+    const int64_t n = op->n;
+    const bool b_real = b_dtype != cdt;
+    const size_t csz = dtype_size(cdt), bsz = dtype_size(b_dtype);
+    if (b_real && b && w && b_loc == w_loc) {      // a real b is half as long as w: it cannot stand in w's place
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(b), w0 = reinterpret_cast<uintptr_t>(w);
+      if (b0 == w0 || (b0 < w0 + (size_t)n * csz && w0 < b0 + (size_t)n * bsz))
+        fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_realop: a real b overlaps w (b and w may be the same vector only when b is complex)");
+    }
+    taylor_check(*op, 0.0, precision, opnorm);      // (precision, a matrix-free operator's opnorm: the messages of expv_taylor)
+    if (n == 0) return;
+    if (!b || !w) fail(EXPV_MI_ARGUMENT_ERROR, "expv_taylor_realop: null pointer");
+    ctx->use();
+    DevBuf tmp;
+    const void *bd = vector_in(ctx, *op, b, b_loc, n, bsz, tmp);
+    TaylorCall tc;
+    taylor_realop_enqueue(ctx, *op, t_re, t_im, bd, b_real, precision, max_matvecs, opnorm, tc);
+    taylor_deliver(ctx, *op, tc, w, w_loc, info, dinfo, csz);
   });
 }
 int expv_mi_expv_taylor_block(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *B, int64_t ldb, int ncols,

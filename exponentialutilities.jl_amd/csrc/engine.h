@@ -628,6 +628,16 @@ double taylor_rownorm(Ctx *ctx, Op &op, double sigma_re, double sigma_im);
 void taylor_power_enqueue(Ctx *ctx, Op &op, const std::function<Op &()> &adj, double t_re, double t_im, const void *b_dev, int precision, int64_t max_matvecs,
                           TaylorCall &tc, int64_t pinfo[3], double d[8]);
 
+// ---- expv_taylor_realop.hip ---------------------------------------------------------------
+// exp(tA)b for a REAL operator (F64 / F32) with t = t_re + i t_im and vectors of its complex type (include/expv_mi.h:
+// expv_mi_expv_taylor_realop).  As taylor_enqueue: b_dev is on the device in the operator's stored ordering, of the complex type or --
+// b_real -- of the operator's own (widened on the device); tc.F is the complex result, taylor_collect fills info / dinfo.
+// taylor_shift_plan_realop (expv_taylor.hip) is taylor_shift_plan for that call: the same plan without the refusal of a complex t.
+void taylor_shift_plan_realop(Ctx *ctx, Op &op, double t_re, double t_im, int precision, int64_t max_matvecs, double opnorm, void *head,
+                              TaylorCall &tc);
+void taylor_realop_enqueue(Ctx *ctx, Op &op, double t_re, double t_im, const void *b_dev, bool b_real, int precision, int64_t max_matvecs,
+                           double opnorm, TaylorCall &tc);
+
 // ---- op_normest.hip -----------------------------------------------------------------------
 // A lower bound of ||(A - sigma I)^p||_inf (which = 0) or _1 (which = 1) by the block 1-norm estimator (include/expv_mi.h:
 // expv_mi_op_norm_power); adj is the operator of A' (op itself for a Hermitian one); the arguments have been checked.  info[0..5].

@@ -270,6 +270,14 @@ void taylor_shift_plan(Ctx *c, Op &op, double t_re, double t_im, int precision, 
     taylor_shift_plan_T<T>(c, op, std::complex<double>(t_re, t_im), precision, max_matvecs, opnorm, head, tc);
   });
 }
+// The plan of a REAL operator for a complex t (expv_taylor_realop.hip): the checks of taylor_check that do not concern t, then the
+// same kernels in the operator's real type -- mu is real, alpha = |t| ||A - mu I||_inf.
+void taylor_shift_plan_realop(Ctx *c, Op &op, double t_re, double t_im, int precision, int64_t max_matvecs, double opnorm, void *head,
+                              TaylorCall &tc) {
+  taylor_check(op, 0.0, precision, opnorm);
+  if (op.dtype == EXPV_MI_F32) taylor_shift_plan_T<float>(c, op, std::complex<double>(t_re, t_im), precision, max_matvecs, opnorm, head, tc);
+  else taylor_shift_plan_T<double>(c, op, std::complex<double>(t_re, t_im), precision, max_matvecs, opnorm, head, tc);
+}
 void taylor_run(Ctx *c, Op &op, double t_re, double t_im, const void *b_dev, void *state, void *v0, void *v1, void *F, TaylorCall &tc) {
   dispatch_dtype(op.dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;

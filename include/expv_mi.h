@@ -652,6 +652,34 @@ int expv_mi_expv_error_estimate(expv_mi_ks_t ks, expv_mi_op_t op, double t_re, d
  * [3] |F|_inf when the last stage closed. */
 int expv_mi_expv_taylor(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc, void *w, int w_loc,
                         int precision, int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4]);
+/* w = exp(t A) b for a REAL stored or matrix-free operator (EXPV_MI_F64 / EXPV_MI_F32), t = t_re + i t_im, complex vectors: the
+ * Schroedinger / wave propagation exp(-i t H) b with a real sparse H, a real Jacobian along a complex ray.  The operator is read in
+ * its own real type -- no promoted complex copy is made -- and the series is that of expv_mi_expv_taylor.
+ *   - w always has the operator's complex counterpart (C64 for an F64 operator, C32 for F32).  b_dtype is that complex type or the
+ *     operator's own real type; a real b is widened on the device with im = +0.  b and w may be the same vector only when b is
+ *     complex.  t_im = 0 is allowed: a real time applied to a complex vector.
+ *   - The plan is expv_mi_expv_taylor's, from the same kernels: mu = tr(A) / n (real), alpha = |t| opnorm(A - mu I, Inf), the theta
+ *     table and tol of the operator's real type and `precision`, (m*, s) of expv_mi_host_taylor_params; the max_matvecs refusal, the
+ *     matrix-free opnorm rule and the early returns are the same, with the same messages ("expv_taylor: ..."): t = 0 or alpha = 0
+ *     gives exp(mu t) b, b = 0 gives 0 after no application, n = 0 does nothing.
+ *   - THE ROUNDINGS.  R = the operator's real type, C its complex type.  (A x)_i is accumulated per component in ascending stored
+ *     order: acc.re = fma(a, x.re, acc.re), acc.im = fma(a, x.im, acc.im).  Everything after (A x)_i is the element step of
+ *     expv_mi_expv_taylor in C with mu = (mu, 0) and the complex c = (t / s) / j rounded to C; the stage close is the same kernel.
+ *     CONSEQUENCE: on finite data, a call that takes the fused path ([6] = 1) returns the same values -- == element by element -- as
+ *     expv_mi_expv_taylor on the same operator promoted to C, whenever that call takes the fused path too and keeps the rows in the
+ *     same stored ordering (the grid-patch ordering sizes its tiles by the element type: there the two differ by rounding); only the
+ *     sign of a zero may differ (the complex multiply-add adds -0 x.im, the real one does not).  mu, alpha, m*, s and the
+ *     application count are then identical as well.
+ *   - An operator without a fused form ([6] = 2: SELL with overflow entries, column-blocked storage, dense, matrix-free)
+ *     is applied with its own real mul! to the real plane and to the imaginary plane of v, then one update kernel does the element
+ *     step: a matrix-free callback sees real vectors of n elements, twice per term.  Workspace: three complex vectors, plus four
+ *     real planes on this path.  A reordered operator gets b permuted on entry and w on exit.
+ *   - Refused before any device work, w untouched, EXPV_MI_ARGUMENT_ERROR "expv_taylor_realop: ...": a complex operator (use
+ *     expv_mi_expv_taylor), a b_dtype that is neither of the two types, a real b that overlaps w, an unknown loc.
+ * info / dinfo (may be NULL): as expv_mi_expv_taylor; dinfo[2] = 0.  [2] counts terms; the context's operator-application counter
+ * counts mul! calls and rises by two per term when [6] = 2.  Block, grid, power and phiv forms of this call do not exist. */
+int expv_mi_expv_taylor_realop(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc, int b_dtype, void *w,
+                               int w_loc, int precision, int64_t max_matvecs, double opnorm, int64_t info[8], double dinfo[4]);
 /* Host only: theta_m (m = 1 .. 55) of the table of `precision` (0: tol = 2^-53, 1: tol = 2^-24) -- the positive root of
  * h~_m(x) = tol x, h~_m(x) = (-1)^m log(e^x T_m(-x)), below the first real zero of T_m(-x) (tools/expv_taylor_theta.py). */
 int expv_mi_host_taylor_theta(int precision, int m, double *theta);

@@ -780,6 +780,20 @@ function expv_taylor!(w::MIVector{T}, t::Number, A::MIOperator{T}, b::MIVector{T
     w
 end
 expv_taylor(t::Number, A::MIOperator{T}, b::MIVector{T}; kw...) where {T} = expv_taylor!(similar(b, T, (length(b),)), t, A, b; kw...)
+# A REAL operator with a complex time and complex vectors -- exp(-i t H) b with a real sparse H: the operator is read as it is stored
+# (no promoted complex copy), w is complex, b is complex or real (widened on the device); w may be b only when b is complex.  On an
+# operator with a fused form the values are those of expv_taylor on the promoted operator, element for element.
+function expv_taylor!(w::MIVector{Complex{R}}, t::Number, A::MIOperator{R}, b::MIVector{Tb}; precision::Integer = 0, max_matvecs::Integer = 0,
+                      opnorm = nothing) where {R <: Real, Tb <: Union{R, Complex{R}}}
+    length(w) == length(b) == size(A, 1) || throw(DimensionMismatch("length(w), length(b) and size(A, 1) must agree"))
+    check(ccall((:expv_mi_expv_taylor_realop, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Cint, Cint, Int64, Cdouble, Ptr{Int64}, Ptr{Cdouble}),
+                ctx().h, A.h, real(t), imag(t), b.ptr, DEVICE, dtype(Tb), w.ptr, DEVICE, precision, max_matvecs,
+                opnorm === nothing ? 0.0 : Float64(opnorm), C_NULL, C_NULL), ctx().h)
+    w
+end
+expv_taylor(t::Number, A::MIOperator{R}, b::MIVector{Complex{R}}; kw...) where {R <: Real} = expv_taylor!(similar(b, Complex{R}, (length(b),)), t, A, b; kw...)
+expv_taylor(t::Complex, A::MIOperator{R}, b::MIVector{R}; kw...) where {R <: Real} = expv_taylor!(similar(b, Complex{R}, (length(b),)), t, A, b; kw...)
 # The same with the reference's WHOLE parameter search (:99-121): above the cheap threshold d_p = |t| ||(A - mu I)^p||^(1/p), p = 2 .. 9,
 # are estimated on the device (opnorm_power) -- far fewer applications for a non-normal A; below it the call is expv_taylor!, bit
 # for bit.  adjoint: an operator of A' (nothing: a Hermitian A serves as its own, otherwise one is made for the call).
