@@ -19,6 +19,7 @@ LINCOMB_MAX_TERMS, LINCOMB_IDENTITY = 8, 1                                   # c
 ORTHO_AUTO, ORTHO_MGS, ORTHO_LOWSYNC, ORTHO_PIPELINED = 0, 1, 2, 3
 PATH_FLAGS = {"modular": 1, "two_kernel": 2, "pipeline": 4, "wave": 8, "overlapped": 16, "redo_serial": 32,
               "redo_wave_off": 64, "resident": 128, "patch": 256, "pipelined_lanczos": 512}
+PATH_REAL_OPERATOR = 2048      # not a step form: a mixed call, the real operator read in its own type under a complex subspace (expv.last_stats["real_operator"])
 PATH_FA2_PIPELINED = 1024      # not a step form: which instantiation of the two-kernel step's first kernel ran (expv.last_stats["fa2_pipelined"])
 
 STATUS_NAMES = {
@@ -76,6 +77,7 @@ PROTOTYPES = {
     "expv_mi_ctx_set_pipeline_overlap": (_i, [_vp, _i]),
     "expv_mi_ctx_counters": (_i, [_vp, _pi64]),
     "expv_mi_ctx_selftest": (_i, [_vp, _pi64]),
+    "expv_mi_ctx_last_path": (_i, [_vp, C.POINTER(C.c_int32)]),
     "expv_mi_ctx_set_option": (_i, [_vp, C.c_char_p, _i64]),
     "expv_mi_ctx_get_option": (_i, [_vp, C.c_char_p, _pi64]),
     "expv_mi_last_error": (C.c_char_p, [_vp]),
@@ -112,6 +114,7 @@ PROTOTYPES = {
     "expv_mi_host_patch_order": (_i, [C.c_int64, _vp, _vp, _i, _vp, _vp, _vp]),
     "expv_mi_host_mesh_patch_order": (_i, [C.c_int64, _vp, _vp, _i, _vp, _vp, _vp]),
     "expv_mi_op_apply": (_i, [_vp, _vp, _i, _vp, _i]),
+    "expv_mi_op_apply_complex": (_i, [_vp, _vp, _i, _vp, _i]),
     "expv_mi_gemv_block": (_i, [_vp, _i, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i]),
     "expv_mi_expm": (_i, [_vp, _i, _i64, _vp, _i64, _i, _vp]),
     "expv_mi_expm_balanced": (_i, [_vp, _i, _i64, _vp, _i64, _i, _vp]),
@@ -135,6 +138,7 @@ PROTOTYPES = {
     "expv_mi_phiv_ks": (_i, [_vp, _d, _d, _i, _i, _vp, _i64, _i, _i, _pd]),
     "expv_mi_combine": (_i, [_vp, _i, _i, _vp, _i, _i, _d, _vp, _i64, _i, _i]),
     "expv_mi_expv": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, C.POINTER(ArnoldiOpts), C.POINTER(ExpvStats)]),
+    "expv_mi_expv_realop": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, C.POINTER(ArnoldiOpts), C.POINTER(ExpvStats)]),
     "expv_mi_expv_error_estimate": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _d, _d, _i, _i]),
     "expv_mi_expv_taylor": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, _i64, _d, _pi64, _pd]),
     "expv_mi_expv_taylor_realop": (_i, [_vp, _vp, _d, _d, _vp, _i, _i, _vp, _i, _i, _i64, _d, _pi64, _pd]),
@@ -153,6 +157,8 @@ PROTOTYPES = {
     "expv_mi_timestep_caches_destroy": (_i, [_vp]),
     "expv_mi_phiv_timestep": (_i, [_vp, _vp, _i, _pd, _vp, _i64, _i, _i, _vp, _i64, _i, C.POINTER(TimestepOpts),
                                    _vp, C.POINTER(TimestepStats)]),
+    "expv_mi_phiv_timestep_realop": (_i, [_vp, _vp, _i, _pd, _vp, _i64, _i, _i, _vp, _i64, _i, C.POINTER(TimestepOpts),
+                                          _vp, C.POINTER(TimestepStats)]),
     "expv_mi_kiops_opts_default": (None, [C.POINTER(KiopsOpts)]),
     "expv_mi_kiops": (_i, [_vp, _vp, _pd, _i, _i, _vp, _i64, _i, _i, _vp, _i64, _i, C.POINTER(KiopsOpts), _pi64]),
     "expv_mi_expv_batch": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _i64, _i, _pd, _vp, _i64, _i, _vp, _i64, _i,

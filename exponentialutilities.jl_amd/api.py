@@ -123,6 +123,14 @@ class Context:
         keys = ("krylov_steps", "factorisations", "pipeline", "overlapped", "redo_serial", "redo_wave_off", "op_applies", "h_by_copy")
         return dict(zip(keys, (int(v) for v in out)))
 
+    def last_path(self):
+        """Step form of the most recent factorisation on this context (expv_mi_ctx_last_path): {"path": names of L.PATH_FLAGS,
+        "fa2_pipelined", "real_operator"} -- what expv.last_stats reports, for arnoldi_ / lanczos_ and the drivers too."""
+        f = C.c_int32(0)
+        _check(L.load().expv_mi_ctx_last_path(self._h, C.byref(f)), self._h)
+        return {"path": [k for k, v in L.PATH_FLAGS.items() if f.value & v], "fa2_pipelined": bool(f.value & L.PATH_FA2_PIPELINED),
+                "real_operator": bool(f.value & L.PATH_REAL_OPERATOR)}
+
     def set_pipeline_overlap(self, on=True):
         """Banded pipeline: consecutive Krylov steps on two streams (default) or one launch after the other."""
         _check(L.load().expv_mi_ctx_set_pipeline_overlap(self._h, int(bool(on))), self._h)
@@ -1353,6 +1361,20 @@ class MIOperator:
         ya.finish()
         return y
 
+    def matvec_complex(self, x, out=None):
+        """mul!(y, A, x) for a REAL operator and complex vectors (expv_mi_op_apply_complex): the operator is read as it is stored, no
+        promoted copy.  ``x``: numpy / torch (device) / DeviceArray, converted to the operator's complex type; ``out``: an optional
+        vector of that type.  A complex operator raises (ArgumentError naming expv_mi_op_apply)."""
+        Cd = _complex_of(self.dtype)
+        xa = _Arg(x, Cd)
+        y = _empty_like(x, (self.shape[0],), Cd) if out is None else out
+        ya = _Arg(y, Cd, writable=True)
+        if int(np.prod(xa.shape)) != self.shape[1] or int(np.prod(ya.shape)) != self.shape[0]:
+            raise DimensionMismatch(f"mul!: A is {self.shape[0]} x {self.shape[1]}, x has {int(np.prod(xa.shape))}, y has {int(np.prod(ya.shape))}")
+        _check(L.load().expv_mi_op_apply_complex(self._h, xa.ptr, xa.loc, ya.ptr, ya.loc), self.ctx._h)
+        ya.finish()
+        return y
+
     __matmul__ = matvec
 
 
@@ -1442,6 +1464,20 @@ def _as_operator(A, want_dtype=None, ctx=None):
         if want != op.dtype:
             op = op.astype(want)
     return op
+
+
+def _is_mixed(op, T):
+    """a real operator whose complex counterpart is the vectors' work type T: what ``keep_real=True`` hands to the mixed entries"""
+    return np.dtype(op.dtype).kind != "c" and np.dtype(T).kind == "c" and _complex_of(op.dtype) == np.dtype(T)
+
+
+def _as_operator_for(A, T, ctx, keep_real):
+    """_as_operator(A, T, ctx), except that with ``keep_real`` a real operator meeting complex vectors of its own precision is not
+    promoted (no second, complex operator: a mixed call)"""
+    if not keep_real:
+        return _as_operator(A, T, ctx)
+    op = _as_operator(A, None, ctx)
+    return op if _is_mixed(op, T) else _as_operator(op, T, ctx)
 
 
 def plan_cache(clear=False, capacity=None):
@@ -1539,11 +1575,12 @@ def _opts(m=None, tol=1e-7, iop=0, init=0, ishermitian=None, ortho="auto", flags
     return o
 
 
-def arnoldi_(Ks, A, b, *, tol=1e-7, m=None, ishermitian=None, opnorm=None, iop=0, init=0, ortho="auto", defer_tail=True):
+def arnoldi_(Ks, A, b, *, tol=1e-7, m=None, ishermitian=None, opnorm=None, iop=0, init=0, ortho="auto", defer_tail=True, keep_real=False):
     """arnoldi!(Ks, A, b; tol, m, ishermitian, opnorm, iop, init)  (arnoldi.jl:345-377).
-    ``opnorm`` is accepted and ignored, like the reference."""
-    op = _as_operator(A, Ks.T, Ks.ctx)
-    if op.dtype != Ks.T:
+    ``opnorm`` is accepted and ignored, like the reference.  ``keep_real=True``: a real operator under a complex subspace of its
+    precision is used as it is stored (a mixed call, include/expv_mi.h) instead of being promoted through ``astype``."""
+    op = _as_operator_for(A, Ks.T, Ks.ctx, keep_real)
+    if op.dtype != Ks.T and not (keep_real and _is_mixed(op, Ks.T)):
         raise TypeError(f"operator eltype {op.dtype} does not fit KrylovSubspace{{{Ks.T}}}")
     ba = _Arg(b, Ks.T)
     if int(np.prod(ba.shape)) != op.shape[0]:
@@ -1556,9 +1593,10 @@ def arnoldi_(Ks, A, b, *, tol=1e-7, m=None, ishermitian=None, opnorm=None, iop=0
     return Ks
 
 
-def lanczos_(Ks, A, b, *, tol=1e-7, m=None, opnorm=None, init=0, ortho="auto"):
-    """lanczos!(Ks, A, b; tol, m)  (arnoldi.jl:456-490).  ``ortho="pipelined"``: the opt-in pipelined recurrence (include/expv_mi.h)."""
-    op = _as_operator(A, Ks.T, Ks.ctx)
+def lanczos_(Ks, A, b, *, tol=1e-7, m=None, opnorm=None, init=0, ortho="auto", keep_real=False):
+    """lanczos!(Ks, A, b; tol, m)  (arnoldi.jl:456-490).  ``ortho="pipelined"``: the opt-in pipelined recurrence (include/expv_mi.h).
+    ``keep_real``: as in arnoldi_."""
+    op = _as_operator_for(A, Ks.T, Ks.ctx, keep_real)
     ba = _Arg(b, Ks.T)
     if int(np.prod(ba.shape)) != op.shape[0]:
         raise DimensionMismatch("length(b) == size(A,1) doesn't hold")
@@ -1569,11 +1607,11 @@ def lanczos_(Ks, A, b, *, tol=1e-7, m=None, opnorm=None, init=0, ortho="auto"):
 
 def arnoldi(A, b, *, m=None, ishermitian=None, **kw):
     """arnoldi(A, b; m = min(30, size(A,1)), ishermitian = LinearAlgebra.ishermitian(A), kwargs...)
-    (arnoldi.jl:161-180)."""
+    (arnoldi.jl:161-180).  ``keep_real``: as in arnoldi_."""
     bdt = _np_dtype_of(b)
     op = _as_operator(A, None)
     T = _work_dtype(op.dtype, bdt)
-    op = _as_operator(op, T)
+    op = _as_operator_for(op, T, None, kw.get("keep_real", False))
     if m is None:
         m = min(30, op.shape[0])
     if ishermitian is None:
@@ -1621,8 +1659,10 @@ def expv(t, A, b=None, *, mode="happy_breakdown", **kw):
         # expv(t, A, b) = arnoldi + expv! (krylov_phiv.jl:135-144) as ONE library call: the subspace is
         # private to the call, so the library reuses its workspace and skips v_{m+1} / H[m+1, m]
         T = _work_dtype(op.dtype, bdt)
-        opT = _as_operator(op, T)
-        extra = set(kw) - {"m", "tol", "iop", "ishermitian", "ortho", "opnorm", "out"}
+        # keep_real=True: a real operator meeting a complex b stays as it is stored (expv_mi_expv_realop: no promoted copy)
+        opT = _as_operator_for(op, T, None, kw.get("keep_real", False))
+        mixed = opT.dtype != T
+        extra = set(kw) - {"m", "tol", "iop", "ishermitian", "ortho", "opnorm", "out", "keep_real"}
         if extra:
             raise TypeError(f"unexpected keyword(s) {sorted(extra)}")
         ish = kw.get("ishermitian")
@@ -1635,14 +1675,19 @@ def expv(t, A, b=None, *, mode="happy_breakdown", **kw):
         if int(np.prod(ba.shape)) != op.shape[0]:
             raise DimensionMismatch(f"length(b) [{int(np.prod(ba.shape))}] == size(A,1) [{op.shape[0]}] doesn't hold")
         st = L.ExpvStats()
-        _check(L.load().expv_mi_expv(opT.ctx._h, opT._h, tr, ti, ba.ptr, ba.loc, wa.ptr, wa.loc, _code(wa.dtype),
-                                     C.byref(o), C.byref(st)), opT.ctx._h)
+        if mixed:
+            _check(L.load().expv_mi_expv_realop(opT.ctx._h, opT._h, tr, ti, ba.ptr, ba.loc, wa.ptr, wa.loc,
+                                                C.byref(o), C.byref(st)), opT.ctx._h)
+        else:
+            _check(L.load().expv_mi_expv(opT.ctx._h, opT._h, tr, ti, ba.ptr, ba.loc, wa.ptr, wa.loc, _code(wa.dtype),
+                                         C.byref(o), C.byref(st)), opT.ctx._h)
         wa.finish()
         if kw.get("out") is None:
             w = _round_to(w, _ref_dtype(_t_dtype(t), getattr(op, "src_dtype", op.dtype), bdt))
         expv.last_stats = {"m": st.m_used, "wasbreakdown": bool(st.wasbreakdown), "matvecs": st.matvecs, "beta": st.beta,
                            "path": [k for k, v in L.PATH_FLAGS.items() if st.path_flags & v],
-                           "fa2_pipelined": bool(st.path_flags & L.PATH_FA2_PIPELINED)}
+                           "fa2_pipelined": bool(st.path_flags & L.PATH_FA2_PIPELINED),
+                           "real_operator": bool(st.path_flags & L.PATH_REAL_OPERATOR)}
         return w
     if mode == "error_estimate":        # _expv_ee  (:145-160)
         m = kw.pop("m", min(30, op.shape[0]))
@@ -2167,12 +2212,14 @@ def timestep_caches(u_prototype, maxiter, p, ctx=None):
 
 def phiv_timestep_(U, ts, A, B, *, tau=0.0, m=None, tol=1e-7, opnorm=None, iop=0, correct=False, caches=None,
                    adaptive=False, delta=1.2, ishermitian=None, gamma=0.8, NA=0, verbose=False, ortho="auto",
-                   out=None, stats=None, reuse_basis=True):
-    """phiv_timestep!(U, ts, A, B; ...)  (krylov_phiv_adaptive.jl:260-453).  ``ts`` is sorted in place."""
+                   out=None, stats=None, reuse_basis=True, keep_real=False):
+    """phiv_timestep!(U, ts, A, B; ...)  (krylov_phiv_adaptive.jl:260-453).  ``ts`` is sorted in place.  ``keep_real=True``: a real
+    operator meeting complex ``B`` / ``U`` of its precision is used as it is stored (expv_mi_phiv_timestep_realop)."""
     Bdt = _np_dtype_of(B)
     T = _work_dtype(Bdt)
-    op = _as_operator(A, T)
-    if op.dtype != T:
+    op = _as_operator_for(A, T, None, keep_real)
+    mixed = bool(keep_real) and _is_mixed(op, T)
+    if op.dtype != T and not mixed:
         T = _work_dtype(op.dtype, T)
     n = op.shape[0]
     Ba = _Arg(B, T)
@@ -2207,7 +2254,8 @@ def phiv_timestep_(U, ts, A, B, *, tau=0.0, m=None, tol=1e-7, opnorm=None, iop=0
     cb = L.PRINT_FN(lambda line, user: sink(line.decode()))
     o.print = cb
     st = L.TimestepStats()
-    _check(L.load().expv_mi_phiv_timestep(op.ctx._h, op._h, int(nsnap), ts_arr.ctypes.data_as(L._pd), Ba.ptr, Ba.ld,
+    entry = L.load().expv_mi_phiv_timestep_realop if mixed else L.load().expv_mi_phiv_timestep
+    _check(entry(op.ctx._h, op._h, int(nsnap), ts_arr.ctypes.data_as(L._pd), Ba.ptr, Ba.ld,
                                           int(ncoef), Ba.loc, Ua.ptr, Ua.ld, Ua.loc, C.byref(o),
                                           caches._h if caches is not None else None, C.byref(st)), op.ctx._h)
     Ua.finish()

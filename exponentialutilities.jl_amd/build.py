@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libexpv_mi.so")
-SOURCES = ["kernels.hip", "op_ingest.hip", "op_coo.hip", "op_bsr.hip", "op_dia.hip", "op_adjoint.hip", "op_lincomb.hip", "fused.hip", "pipe.hip", "lanczos_pl.hip", "engine_core.hip", "engine_drivers.hip", "engine_batch.hip", "dense_dev.hip", "expv_taylor.hip", "expv_taylor_realop.hip", "expv_taylor_block.hip", "expv_taylor_grid.hip", "phiv_taylor.hip", "capi.hip", "op_normest.hip"]
+SOURCES = ["kernels.hip", "op_ingest.hip", "op_coo.hip", "op_bsr.hip", "op_dia.hip", "op_adjoint.hip", "op_lincomb.hip", "fused.hip", "pipe.hip", "lanczos_pl.hip", "engine_core.hip", "engine_drivers.hip", "engine_batch.hip", "dense_dev.hip", "expv_taylor.hip", "expv_taylor_realop.hip", "krylov_realop.hip", "expv_taylor_block.hip", "expv_taylor_grid.hip", "phiv_taylor.hip", "capi.hip", "op_normest.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Xarch_host", "-mavx2", "-Xarch_host", "-mfma",
          "-Xarch_host", "-fcx-limited-range"]   # complex products of the host small-dense code: plain (ac-bd, ad+bc), no __muldc3 NaN recovery   # host small-dense exp: every MI355X host is x86-64-v3

@@ -1505,6 +1505,11 @@ int expv_mi_ctx_counters(expv_mi_ctx_t ctx, int64_t out[8]) {
   out[4] = ctx->cnt_serial_redo; out[5] = ctx->cnt_wave_redo; out[6] = ctx->cnt_opapply; out[7] = ctx->cnt_copy;
   return EXPV_MI_OK;
 }
+int expv_mi_ctx_last_path(expv_mi_ctx_t ctx, int32_t *path_flags) {
+  if (!ctx || !path_flags) return EXPV_MI_ARGUMENT_ERROR;
+  *path_flags = ctx->last_path;
+  return EXPV_MI_OK;
+}
 int expv_mi_ctx_selftest(expv_mi_ctx_t ctx, int64_t out[8]) {
   if (!out) return EXPV_MI_ARGUMENT_ERROR;
   return guarded(ctx, [&] {
@@ -2699,6 +2704,33 @@ int expv_mi_op_apply(expv_mi_op_t op, const void *x, int x_loc, void *y, int y_l
   });
 }
 
+int expv_mi_op_apply_complex(expv_mi_op_t op, const void *x, int x_loc, void *y, int y_loc) {
+  return guarded(op->ctx, [&] {
+    Ctx *c = op->ctx;
+    c->use();
+    if (dtype_is_complex(op->dtype))
+      fail(EXPV_MI_ARGUMENT_ERROR, "op_apply_complex: the operator is complex; expv_mi_op_apply is the call for a complex operator");
+    const size_t esz = dtype_size(dtype_complex_of(op->dtype));
+    const size_t bytes = (size_t)op->n * esz;
+    DevBuf xt, yt, work;
+    if (op->perm) {      // stored as P A P':  y = P' ((P A P') (P x))
+      int64_t ldx = op->n;
+      const void *xp = permute_in(c, *op->perm, x, x_loc, 1, op->n, esz, xt, &ldx);
+      yt.take_from(c, bytes + 16);
+      op_apply_mixed(*op, xp, yt.p, nullptr, 0, work);
+      permute_out(c, *op->perm, yt.p, op->n, y, y_loc, op->n, 1, esz);
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      return;
+    }
+    const void *xd = stage_in(c, x, x_loc, bytes, xt);
+    void *yd = y;
+    if (y_loc == EXPV_MI_HOST) { yt.alloc(bytes + 16); yd = yt.p; }
+    op_apply_mixed(*op, xd, yd, nullptr, 0, work);
+    if (y_loc == EXPV_MI_HOST) HIPCHECK(hipMemcpyAsync(y, yd, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+  });
+}
+
 int expv_mi_gemv_block(expv_mi_ctx_t ctx, int dtype, int64_t nrows, int64_t ncols, const void *A, int64_t lda,
                        const void *x, void *y, void *scratch, int nsplit) {
   return guarded(ctx, [&] {
@@ -3055,8 +3087,9 @@ int expv_mi_combine(expv_mi_ks_t ks, int mcols, int ncols, const void *coef_host
   });
 }
 
-int expv_mi_expv(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc, void *w,
-                 int w_loc, int w_dtype, const expv_mi_arnoldi_opts *opts, expv_mi_expv_stats *stats) {
+// expv_mi_expv (vdt = the operator's dtype) and expv_mi_expv_realop (vdt = its complex counterpart): b and the private subspace have vdt
+static int expv_call(expv_mi_ctx_t ctx, expv_mi_op_t op, int vdt, double t_re, double t_im, const void *b, int b_loc, void *w,
+                     int w_loc, int w_dtype, const expv_mi_arnoldi_opts *opts, expv_mi_expv_stats *stats) {
   return guarded(ctx, [&] {
     expv_mi_arnoldi_opts o;
     if (opts) o = *opts; else expv_mi_arnoldi_opts_default(&o);
@@ -3066,14 +3099,14 @@ int expv_mi_expv(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, c
     // the internal subspace is private to this call: reuse it across calls of the same shape, and skip what
     // expv never reads (v_{m+1}, H[m+1, m])
     ht_mark(0);
-    const int dtU = herm ? dtype_real_of(op->dtype) : op->dtype;
+    const int dtU = herm ? dtype_real_of(vdt) : vdt;
     expv_mi_ks_s *kp = reinterpret_cast<expv_mi_ks_s *>(ctx->ws_ks);
-    if (!kp || kp->dtypeT != op->dtype || kp->dtypeU != dtU || kp->n != op->n || kp->maxiter != m || kp->augmented != 0) {
+    if (!kp || kp->dtypeT != vdt || kp->dtypeU != dtU || kp->n != op->n || kp->maxiter != m || kp->augmented != 0) {
       delete kp;
       ctx->ws_ks = nullptr;
       kp = new expv_mi_ks_s();
       ctx->ws_ks = kp;
-      ks_alloc(*kp, ctx, op->dtype, dtU, op->n, m, 0);
+      ks_alloc(*kp, ctx, vdt, dtU, op->n, m, 0);
     }
     expv_mi_ks_s &ks = *kp;
     ks.skip_tail = true;
@@ -3081,10 +3114,10 @@ int expv_mi_expv(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, c
     const void *bd;
     FactorisationScope scope(ks, 0);
     if (op->perm) {      // b stays in the caller's ordering: the engine gathers it in its first step
-      bd = stage_in(ctx, b, b_loc, (size_t)op->n * dtype_size(op->dtype), tmp);
+      bd = stage_in(ctx, b, b_loc, (size_t)op->n * dtype_size(vdt), tmp);
       ks.b_natural = true;
     } else {
-      bd = vector_in(ctx, *op, b, b_loc, op->n, dtype_size(op->dtype), tmp);
+      bd = vector_in(ctx, *op, b, b_loc, op->n, dtype_size(vdt), tmp);
     }
     ks.vperm = op->perm;      // (expv_eval puts the rows of w back in their natural places)
     const int mv = arnoldi_run(ks, *op, bd, o, nullptr, false);
@@ -3099,6 +3132,17 @@ int expv_mi_expv(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, c
       stats->path_flags = ctx->last_path;
     }
   });
+}
+int expv_mi_expv(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc, void *w,
+                 int w_loc, int w_dtype, const expv_mi_arnoldi_opts *opts, expv_mi_expv_stats *stats) {
+  return expv_call(ctx, op, op->dtype, t_re, t_im, b, b_loc, w, w_loc, w_dtype, opts, stats);
+}
+int expv_mi_expv_realop(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc, void *w,
+                        int w_loc, const expv_mi_arnoldi_opts *opts, expv_mi_expv_stats *stats) {
+  if (ctx && op && dtype_is_complex(op->dtype))
+    return guarded(ctx, [&] { fail(EXPV_MI_ARGUMENT_ERROR, "expv_realop: the operator is complex; expv_mi_expv is the call for a complex operator"); });
+  const int cdt = dtype_complex_of(op->dtype);
+  return expv_call(ctx, op, cdt, t_re, t_im, b, b_loc, w, w_loc, cdt, opts, stats);
 }
 
 int expv_mi_expv_error_estimate(expv_mi_ks_t ks, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc,
@@ -3478,6 +3522,18 @@ int expv_mi_phiv_timestep(expv_mi_ctx_t ctx, expv_mi_op_t op, int nts, double *t
     expv_mi_timestep_opts o;
     if (opts) o = *opts; else expv_mi_timestep_opts_default(&o);
     phiv_timestep_run(ctx, *op, nts, ts, B, ldb, ncoef, b_loc, U, ldu, u_loc, o, caches, stats);
+  });
+}
+
+int expv_mi_phiv_timestep_realop(expv_mi_ctx_t ctx, expv_mi_op_t op, int nts, double *ts, const void *B, int64_t ldb, int ncoef,
+                                 int b_loc, void *U, int64_t ldu, int u_loc, const expv_mi_timestep_opts *opts,
+                                 expv_mi_tscache_t caches, expv_mi_timestep_stats *stats) {
+  return guarded(ctx, [&] {
+    if (dtype_is_complex(op->dtype))
+      fail(EXPV_MI_ARGUMENT_ERROR, "phiv_timestep_realop: the operator is complex; expv_mi_phiv_timestep is the call for a complex operator");
+    expv_mi_timestep_opts o;
+    if (opts) o = *opts; else expv_mi_timestep_opts_default(&o);
+    phiv_timestep_run(ctx, *op, nts, ts, B, ldb, ncoef, b_loc, U, ldu, u_loc, o, caches, stats, dtype_complex_of(op->dtype));
   });
 }
 

@@ -638,6 +638,16 @@ void taylor_shift_plan_realop(Ctx *ctx, Op &op, double t_re, double t_im, int pr
 void taylor_realop_enqueue(Ctx *ctx, Op &op, double t_re, double t_im, const void *b_dev, bool b_real, int precision, int64_t max_matvecs,
                            double opnorm, TaylorCall &tc);
 
+// ---- krylov_realop.hip --------------------------------------------------------------------
+// A MIXED call: an operator of a real dtype with vectors / a subspace of its complex counterpart (include/expv_mi.h).
+// op_apply_mixed: mul!(y, A, x) for device vectors of the complex type in the operator's stored ordering -- one kernel on an
+// operator with a fused form (taylor_fused; counts one application), the operator's own real mul! on each plane otherwise (two);
+// `work` keeps the four planes of the second path between calls.  fused_a2_realop: the first kernel of the two-kernel step with
+// y~ from the real operator (fa.A and the other operator fields of fa are not read).
+void op_apply_mixed(Op &op, const void *x_dev, void *y_dev, const StepState *st, int step, DevBuf &work);
+template <class C> void fused_a2_realop(Ctx *c, const Op &op, const dev::FusedAArgs<C> &fa, double tol);
+inline bool dtype_mixed_pair(int op_dtype, int vec_dtype) { return !dtype_is_complex(op_dtype) && dtype_is_complex(vec_dtype) && vec_dtype == dtype_complex_of(op_dtype); }
+
 // ---- op_normest.hip -----------------------------------------------------------------------
 // A lower bound of ||(A - sigma I)^p||_inf (which = 0) or _1 (which = 1) by the block 1-norm estimator (include/expv_mi.h:
 // expv_mi_op_norm_power); adj is the operator of A' (op itself for a Hermitian one); the arguments have been checked.  info[0..5].
@@ -677,7 +687,7 @@ int phiv_taylor_pmax();
 // ---- engine_drivers.hip --------------------------------------------------------------------
 void phiv_timestep_run(Ctx *ctx, Op &op, int nts, double *ts, const void *B, int64_t ldb, int ncoef, int b_loc,
                        void *U, int64_t ldu, int u_loc, const expv_mi_timestep_opts &o, TsCache *cache,
-                       expv_mi_timestep_stats *stats);
+                       expv_mi_timestep_stats *stats, int vec_dtype = -1);      // vec_dtype: of B, U and the caches (-1: the operator's)
 void kiops_run(Ctx *ctx, Op &op, const double *tau_out, int ntau, int tau_ncols, const void *u, int64_t ldu,
                int ncols_u, int u_loc, void *w, int64_t ldw, int w_loc, const expv_mi_kiops_opts &o, int64_t stats[5]);
 void expv_error_estimate_run(Ks &ks, Op &op, double t_re, double t_im, const void *b, int b_loc, void *w, int w_loc,

@@ -489,6 +489,8 @@ struct ArnoldiCall {
   bool cont_reset_done = false; // reset_device_state() did the whole reset of a continued single-pass factorisation in one launch
   bool tail_deferred = false;   // read_back() returned at the early mailbox flag (Ks::defer_tail_req)   // first_step() zeroed this call's columns of Hdev together with the step state
   bool use_fused = false, single_red = false, use_pipe = false, use_wave = false, use_ring = false, mbox_generic = false;
+  bool mixed = false;                 // a real operator under a complex subspace (krylov_realop.hip): two-kernel or modular step only
+  DevBuf mixed_work;                  // ... the planes of its modular mul! on an operator without a fused form
   const int32_t *b_map = nullptr;     // the first step gathers b through this (b in the caller's ordering, basis in the operator's)
   bool b_nat = false;                 // ... b arrived that way (a redo of the call has to be told again)
 
@@ -507,7 +509,11 @@ struct ArnoldiCall {
     // checkdims (arnoldi.jl:207-220)
     if (op.n != ks.n || p != ks.augmented)
       fail(EXPV_MI_DIMENSION_MISMATCH, "length(b') == size(A,1) == size(A,2) == size(V,1)-p doesn't hold");
-    if (op.dtype != ks.dtypeT) fail(EXPV_MI_ARGUMENT_ERROR, "operator dtype must equal the subspace dtype T");
+    if (op.dtype != ks.dtypeT) {
+      if (!dtype_mixed_pair(op.dtype, ks.dtypeT)) fail(EXPV_MI_ARGUMENT_ERROR, "operator dtype must equal the subspace dtype T");
+      if (isaug) fail(EXPV_MI_ARGUMENT_ERROR, "arnoldi_aug: real operator with complex vectors is not supported here");
+      mixed = true;
+    }
     rows = ks.rows();
     V = ks.V.as<T>();
     st = ks.state.as<StepState>();
@@ -699,6 +705,10 @@ struct ArnoldiCall {
       use_wave = true;
       wave_reach = reach_rows;
     }
+  }
+  if (mixed) {      // the operator in its own real type: the two-kernel step on a fused-form operator, the modular launches otherwise
+    use_pipe = use_wave = use_ring = false;
+    use_fused = use_fused && single_red && taylor_fused(op);
   }
   if (!fresh) {
     // a continuation (init > 0: kiops after a rejected step, arnoldi!(...; init)) reads the stored, NORMALISED basis: its
@@ -1097,6 +1107,12 @@ struct ArnoldiCall {
       d.real_coeff = real_coeff;
       d.Hdev = Hd; d.ldh = ks.ldhd; d.jcol = j - 1; d.gram = ks.gram.as<T>(); d.ldg = ks.ldg; d.jrow = j - 1;
       d.hcoef = hcoef;
+      if (mixed) {      // y~ from the operator in its own real type (krylov_realop.hip); the rest of the step is the complex type's
+        if constexpr (ST<T>::is_complex) {
+          ProfScope ps(c, EXPV_MI_K_FUSED_A);
+          fused_a2_realop<T>(c, op, fa, tol);
+        }
+      } else
       { ProfScope ps(c, EXPV_MI_K_FUSED_A); fa2_pl_used |= dev::fused_a2<T>(s, fa, tol); }
       dev::UpdateArgs<T> u{};
       u.V = V; u.ldv = ks.ldv; u.n = rows; u.y = V + (size_t)j * ks.ldv; u.yin = yb;
@@ -1161,7 +1177,8 @@ struct ArnoldiCall {
     for (int j = jstart; j <= m; ++j) {
       const T *x = V + (size_t)(j - 1) * ks.ldv;
       T *y = V + (size_t)j * ks.ldv;
-      op_apply_T<T>(op, x, y, st, j);
+      if (mixed) op_apply_mixed(op, x, y, st, j, mixed_work);
+      else op_apply_T<T>(op, x, y, st, j);
       if (isaug) {
         ProfScope ps(c, EXPV_MI_K_AUG);
         dev::aug_apply<T>(s, ks.n, p, reinterpret_cast<const T *>(aug->B), aug->ldb, x, y, st, j);
@@ -1340,6 +1357,7 @@ struct ArnoldiCall {
   ++c->cnt_fact;
   c->last_path = use_pipe ? (EXPV_MI_PATH_PIPELINE | (use_wave ? EXPV_MI_PATH_WAVE : 0) | (use_ring ? EXPV_MI_PATH_PATCH : 0) | (ks.pipe_live_used ? EXPV_MI_PATH_OVERLAPPED : 0) | (ks.pipe_resident_used ? EXPV_MI_PATH_RESIDENT : 0))
                           : (use_fused ? (EXPV_MI_PATH_TWO_KERNEL | (fa2_pl_used ? EXPV_MI_PATH_FA2_PIPELINED : 0)) : EXPV_MI_PATH_MODULAR);
+  if (mixed) c->last_path |= EXPV_MI_PATH_REAL_OPERATOR;
   if (!from_mbox) ++c->cnt_copy;
   if (use_pipe) { ++c->cnt_pipe; if (ks.pipe_live_used) ++c->cnt_live; }
   return jlast - jstart + 1;
@@ -1666,6 +1684,7 @@ static void error_estimate_T(Ks &ks, Op &op, cd t, const T *b, void *w, int w_lo
   if (m > ks.maxiter) ks_resize(ks, m);
   else ks.m = m;
   if (op.n != ks.n || ks.augmented != 0) fail(EXPV_MI_DIMENSION_MISMATCH, "expv!: operator / subspace size mismatch");
+  if (dtype_mixed_pair(op.dtype, ks.dtypeT)) fail(EXPV_MI_ARGUMENT_ERROR, "expv_error_estimate: real operator with complex vectors is not supported here");
   if (op.dtype != ks.dtypeT) fail(EXPV_MI_ARGUMENT_ERROR, "operator dtype must equal the subspace dtype T");
   if (c->opt.ee_blocked) {
     // Blocks of Lanczos steps through the ordinary factorisation (arnoldi_run: single-pass / overlapped step where the operator

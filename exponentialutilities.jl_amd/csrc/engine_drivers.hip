@@ -113,9 +113,10 @@ struct TsWs : TsCache { expv_mi_ks_s ks_store; };   // the context-cached work s
 
 template <class T>
 static void phiv_timestep_T(Ctx *ctx, Op &op, int nts, double *ts, const T *B, int64_t ldb, int ncoef, T *Udev,
-                            int64_t ldu, const expv_mi_timestep_opts &o, TsCache *cache, expv_mi_timestep_stats *stats) {
+                            int64_t ldu, const expv_mi_timestep_opts &o, TsCache *cache, expv_mi_timestep_stats *stats, int dt) {
   const int64_t n = op.n;
-  const int dt = op.dtype;
+  const bool mixed = dt != op.dtype;      // a real operator under complex vectors (krylov_realop.hip): dt is the vectors' type
+  DevBuf mixed_work;
   int m = o.m > 0 ? o.m : (int)std::min<int64_t>(10, n);
   const double tol = o.tol, delta = o.delta, gamma = o.gamma;
   int iop = o.iop;
@@ -222,8 +223,9 @@ static void phiv_timestep_T(Ctx *ctx, Op &op, int nts, double *ts, const T *B, i
       const void *tin[6];
       double tcf[6];
       for (int l = 0; l < nt && l < 6; ++l) { tin[l] = B + (size_t)(j + l) * ldb; tcf[l] = coeffs[l]; }
-      if (nt <= 6 && op_apply_lincomb_dev(op, W + (size_t)(j - 1) * n, wj, nt, tin, tcf)) continue;
-      op_apply_dev(op, W + (size_t)(j - 1) * n, wj, nullptr, 0);
+      if (!mixed && nt <= 6 && op_apply_lincomb_dev(op, W + (size_t)(j - 1) * n, wj, nt, tin, tcf)) continue;
+      if (mixed) op_apply_mixed(op, W + (size_t)(j - 1) * n, wj, nullptr, 0, mixed_work);
+      else op_apply_dev(op, W + (size_t)(j - 1) * n, wj, nullptr, 0);
       std::vector<const T *> in{wj};
       std::vector<double> cf{1.0};
       for (int l = 0; l <= p - j; ++l) {
@@ -396,12 +398,13 @@ static void phiv_timestep_T(Ctx *ctx, Op &op, int nts, double *ts, const T *B, i
 
 void phiv_timestep_run(Ctx *ctx, Op &op, int nts, double *ts, const void *B, int64_t ldb, int ncoef, int b_loc, void *U,
                        int64_t ldu, int u_loc, const expv_mi_timestep_opts &o, TsCache *cache,
-                       expv_mi_timestep_stats *stats) {
+                       expv_mi_timestep_stats *stats, int vec_dtype) {
   ctx->use();
   const int64_t n = op.n;
   if (nts < 1) fail(EXPV_MI_ASSERTION, "Dimension mismatch: length(ts) == size(U,2)");
   if (ncoef < 1) fail(EXPV_MI_ASSERTION, "Dimension mismatch: B needs at least one column");
-  const size_t esz = dtype_size(op.dtype);
+  if (vec_dtype < 0) vec_dtype = op.dtype;      // (otherwise: the complex counterpart of a real operator, checked by the caller)
+  const size_t esz = dtype_size(vec_dtype);
   DevBuf btmp, utmp;
   int64_t ldbd = ldb;
   // a reordered operator (reorder.h): the whole controller runs in the stored ordering -- B in, the snapshots out
@@ -414,9 +417,9 @@ void phiv_timestep_run(Ctx *ctx, Op &op, int nts, double *ts, const void *B, int
     Ud = utmp.p;
     ldud = n;
   }
-  dispatch_dtype(op.dtype, [&](auto tag) {
+  dispatch_dtype(vec_dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    phiv_timestep_T<T>(ctx, op, nts, ts, (const T *)Bd, ldbd, ncoef, (T *)Ud, ldud, o, cache, stats);
+    phiv_timestep_T<T>(ctx, op, nts, ts, (const T *)Bd, ldbd, ncoef, (T *)Ud, ldud, o, cache, stats, vec_dtype);
   });
   if (op.perm) permute_out(ctx, *op.perm, Ud, ldud, U, u_loc, ldu, nts, esz);
   else if (u_loc == EXPV_MI_HOST) copy_out_2d(ctx, U, EXPV_MI_HOST, ldu, Ud, ldud, n, nts, esz);

@@ -158,16 +158,7 @@ __global__ __launch_bounds__(BLOCK, DOTS_WAVES) void k_fused_a(FusedAArgs<T> fa,
 
 // slices are handed out in contiguous, equal runs per WAVE so that every resident wave streams the
 // same number of bytes (a grid larger than the chip would run a second, partially filled round)
-static void plan_slices(int64_t nslices, int max_blocks, int *nblocks, int *spw) {
-  const int64_t nwaves = (int64_t)max_blocks * (BLOCK / 64);
-  int64_t per = (nslices + nwaves - 1) / nwaves;
-  if (per < 1) per = 1;
-  const int64_t waves = (nslices + per - 1) / per;
-  int64_t nb = (waves + (BLOCK / 64) - 1) / (BLOCK / 64);
-  if (nb < 1) nb = 1;
-  *nblocks = (int)nb;
-  *spw = (int)per;
-}
+// (plan_slices: kernels.h, shared with krylov_realop.hip)
 template <class T>
 void fused_a(hipStream_t s, const FusedAArgs<T> &a) {
   int nb, spw;

@@ -64,6 +64,18 @@ void mailbox_fill(hipStream_t s, const double *Hdev, int64_t nwords, const StepS
 
 // Balanced contiguous partition of n rows over at most max_blocks workgroups, in units of `unit`
 // rows: every workgroup streams the same number of bytes (no second, partially filled round).
+// Slices handed out in contiguous, equal runs per WAVE so that every resident wave streams the same number of bytes (a grid larger than
+// the chip would run a second, partially filled round): the first kernels of the two-kernel step (fused.hip, krylov_realop.hip)
+inline void plan_slices(int64_t nslices, int max_blocks, int *nblocks, int *spw) {
+  const int64_t nwaves = (int64_t)max_blocks * (BLOCK / 64);
+  int64_t per = (nslices + nwaves - 1) / nwaves;
+  if (per < 1) per = 1;
+  const int64_t waves = (nslices + per - 1) / per;
+  int64_t nb = (waves + (BLOCK / 64) - 1) / (BLOCK / 64);
+  if (nb < 1) nb = 1;
+  *nblocks = (int)nb;
+  *spw = (int)per;
+}
 struct RowPlan { int nblocks; int64_t rows_per_block; };
 RowPlan plan_rows(int64_t n, int unit, int max_blocks);
 // ---- values-only update of a CSR operator's stored forms (capi.hip: expv_mi_op_update_values) --------------------------

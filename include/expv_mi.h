@@ -145,6 +145,9 @@ int expv_mi_ctx_get_option(expv_mi_ctx_t ctx, const char *name, int64_t *value);
  * [7] factorisations whose H and state came home by copy + stream synchronisation instead of through the host mailbox (option
  * mailbox = 0, or a step form without one).  A non-zero [4] / [5] means the overlapped / wave form was switched off for the following 64 calls. */
 int expv_mi_ctx_counters(expv_mi_ctx_t ctx, int64_t out[8]);
+/* EXPV_MI_PATH_* flags of the most recent factorisation on the context -- what expv_mi_expv_stats.path_flags reports for a whole-call
+ * expv, for expv_mi_arnoldi / expv_mi_lanczos / the drivers too (0: none yet). */
+int expv_mi_ctx_last_path(expv_mi_ctx_t ctx, int32_t *path_flags);
 /* Device self-test: the cross-lane sums of the kernels run on v_permlane32/16_swap + DPP (no LDS round trip); this runs them
  * against the LDS-permute (shuffle) forms on random values and returns the number of lanes whose result differs in ANY bit:
  * out[0] single exchanges (distances 32 .. 1), [1] 64-lane butterfly total, [2] 32-lane butterfly total, [3] lane 0 of the
@@ -158,7 +161,9 @@ enum {
   EXPV_MI_PATH_RESIDENT = 128,  /* the whole factorisation ran as one resident (cooperative) kernel */
   EXPV_MI_PATH_PATCH = 256,     /* single-pass step, patch form: operator stored in a grid-patch ordering, ring recomputed */
   EXPV_MI_PATH_PIPELINED_LANCZOS = 512,     /* the opt-in pipelined Lanczos recurrence ran (EXPV_MI_ORTHO_PIPELINED) */
-  EXPV_MI_PATH_FA2_PIPELINED = 1024         /* two-kernel step: its first kernel ran in the requests-up-front instantiation (option fa2_pipelined; real types, SELL slots) */
+  EXPV_MI_PATH_FA2_PIPELINED = 1024,        /* two-kernel step: its first kernel ran in the requests-up-front instantiation (option fa2_pipelined; real types, SELL slots) */
+  EXPV_MI_PATH_REAL_OPERATOR = 2048         /* a mixed call: a real operator read in its own type under a complex subspace (see expv_mi_arnoldi); beside
+                                             * EXPV_MI_PATH_TWO_KERNEL or EXPV_MI_PATH_MODULAR, the only two forms such a call runs */
 };
 const char *expv_mi_last_error(expv_mi_ctx_t ctx);
 const char *expv_mi_version(void);
@@ -462,6 +467,15 @@ int expv_mi_host_mesh_patch_order(int64_t n, const int32_t *rowptr, const int32_
                                   int64_t out[8]);
 /* mul!(y, A, x)  (arnoldi.jl:185) */
 int expv_mi_op_apply(expv_mi_op_t op, const void *x, int x_loc, void *y, int y_loc);
+/* mul!(y, A, x) for a REAL operator (F64 / F32) and vectors of its complex type (C64 / C32): the operator is read as it is stored, no
+ * promoted copy.  Host and device locations and reordered operators as in expv_mi_op_apply; complete on return.  An operator with a
+ * fused form (SELL slots without overflow entries, or the general diagonal form under option dia) is walked once against the
+ * interleaved x: one operator value and one complex gather per entry, one fma per component in ascending stored order -- the values
+ * of the promoted operator's mul!.  Every other operator (overflow rows, column-blocked storage, dense, matrix-free) applies its own
+ * real mul! to the real and to the imaginary plane of x: a matrix-free callback sees real n-vectors, twice.  Counter [6] of
+ * expv_mi_ctx_counters counts one application on the first path and two on the second.
+ * A complex operator is EXPV_MI_ARGUMENT_ERROR "op_apply_complex: ...". */
+int expv_mi_op_apply_complex(expv_mi_op_t op, const void *x, int x_loc, void *y, int y_loc);
 
 /* y[0:nrows] = A x for a DEVICE-RESIDENT column-major nrows x ncols block A (leading dimension lda >= nrows), x (ncols) and
  * y (nrows) device vectors, enqueued on the context's stream (stream-ordered: nothing is synchronised).  The same kernel as the
@@ -580,6 +594,17 @@ typedef struct {
  * factorisation must not set it; the Julia shim and the Python mirror fetch H through the call every time and do. */
 #define EXPV_MI_ARNOLDI_DEFER_TAIL 1
 void expv_mi_arnoldi_opts_default(expv_mi_arnoldi_opts *o);
+/* The operator's dtype equals the subspace's dtype_T, or -- a MIXED call, T = promote_type(eltype(A), eltype(b)) with a real A and a
+ * complex b -- the operator is F64 / F32 and dtype_T its complex counterpart C64 / C32; b has dtype_T.  Mathematically a mixed call
+ * is the call on the promoted operator; the operator is never promoted, copied or re-created.  It runs one of two forms
+ * (path_flags carries EXPV_MI_PATH_REAL_OPERATOR): the two-kernel step with the operator walked in its real type, on an operator with
+ * a fused form (see expv_mi_op_apply_complex) when options fused = 1, fused_two_reductions = 0, ortho != MGS and the window is
+ * <= 64 columns (or Lanczos); the modular launches with expv_mi_op_apply_complex's mul! otherwise.  The single-pass, wave, patch,
+ * resident and pipelined-Lanczos forms are off; a reordering of the stored operator stays in force.  ishermitian < 0 asks the
+ * operator: a real symmetric one runs lanczos! with a real tridiagonal H (dtype_U = the real type).  Happy breakdown, a zero b,
+ * init > 0, expv_mi_ks_resize, EXPV_MI_ARNOLDI_DEFER_TAIL and every evaluation of the resulting subspace are those of any call.
+ * Every other mismatch (a complex operator with a real subspace, F64 with C32, F32 with C64) is EXPV_MI_ARGUMENT_ERROR "operator
+ * dtype must equal the subspace dtype T". */
 int expv_mi_arnoldi(expv_mi_ks_t ks, expv_mi_op_t op, const void *b, int b_loc,
                     const expv_mi_arnoldi_opts *opts);
 /* lanczos!(Ks, A, b; ...) called directly (basictests.jl:746) */
@@ -591,6 +616,11 @@ int expv_mi_lanczos(expv_mi_ks_t ks, expv_mi_op_t op, const void *b, int b_loc,
 int expv_mi_arnoldi_aug(expv_mi_ks_t ks, expv_mi_op_t op, const void *B, int64_t ldb, int p, int b_loc,
                         const void *w, int w_loc, double *w_aug_host, double t, double mu,
                         const expv_mi_arnoldi_opts *opts);
+/* (a mixed pair -- real operator, subspace of its complex type -- is EXPV_MI_ARGUMENT_ERROR "arnoldi_aug: real operator with complex
+ *  vectors is not supported here"; so is expv_mi_expv_error_estimate, "expv_error_estimate: ...".  expv_mi_kiops and
+ *  expv_mi_expv_batch take the vectors' type from the operator / the values and cannot be handed such a pair: they have no
+ *  refusal, and complex data passed as u / B beside a real operator is read as real data of the same byte length, as it always was.
+ *  Promote the operator for those two.) */
 
 /* ------------------------------------------------------------------ evaluation ------- */
 /* expv!(w, t, Ks)  (krylov_phiv.jl:200-280): w = beta * V[:,1:m] * exp(t*H[1:m,1:m]) e1.
@@ -614,6 +644,12 @@ typedef struct {
 int expv_mi_expv(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc,
                  void *w, int w_loc, int w_dtype, const expv_mi_arnoldi_opts *opts,
                  expv_mi_expv_stats *stats);
+/* expv_mi_expv for a REAL operator with b and w of its complex type (a mixed call, see expv_mi_arnoldi): exp(-i t H) b with a real
+ * sparse H and a complex b, t = t_re + i t_im.  The private subspace (kept in the context, keyed on the vectors' type) is complex,
+ * its H real when the operator is symmetric; v_{m+1} and H[m+1, m] are skipped as there; b and w may alias as there.  A complex
+ * operator is EXPV_MI_ARGUMENT_ERROR "expv_realop: ...". */
+int expv_mi_expv_realop(expv_mi_ctx_t ctx, expv_mi_op_t op, double t_re, double t_im, const void *b, int b_loc,
+                        void *w, int w_loc, const expv_mi_arnoldi_opts *opts, expv_mi_expv_stats *stats);
 /* expv!(w, t, A, b, Ks, cache; atol, rtol, m)  error-estimate mode, Hermitian only
  * (krylov_phiv_error_estimate.jl:149-207) */
 int expv_mi_expv_error_estimate(expv_mi_ks_t ks, expv_mi_op_t op, double t_re, double t_im, const void *b,
@@ -893,6 +929,13 @@ int expv_mi_phiv_timestep(expv_mi_ctx_t ctx, expv_mi_op_t op, int nts, double *t
                           int64_t ldb, int ncoef, int b_loc, void *U, int64_t ldu, int u_loc,
                           const expv_mi_timestep_opts *opts, expv_mi_tscache_t caches,
                           expv_mi_timestep_stats *stats);
+/* expv_mi_phiv_timestep for a REAL operator with B, U and the caches of its complex type (mixed calls, see expv_mi_arnoldi).  The W
+ * recurrence applies the operator with expv_mi_op_apply_complex's mul! and adds the columns of B in a second pass; ncoef = 1 is
+ * expv_timestep!.  A complex operator is EXPV_MI_ARGUMENT_ERROR "phiv_timestep_realop: ...". */
+int expv_mi_phiv_timestep_realop(expv_mi_ctx_t ctx, expv_mi_op_t op, int nts, double *ts, const void *B,
+                                 int64_t ldb, int ncoef, int b_loc, void *U, int64_t ldu, int u_loc,
+                                 const expv_mi_timestep_opts *opts, expv_mi_tscache_t caches,
+                                 expv_mi_timestep_stats *stats);
 
 /* kiops(tau_out, A, u; mmin, mmax, m, tol, iop, ishermitian, task1)  (kiops.jl:57-281).
  * u is n x ncols_u; w is n x 1 (numSteps = size(tau_out,2) = 1 is the only reachable case, see

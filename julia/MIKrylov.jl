@@ -622,6 +622,12 @@ function LinearAlgebra.mul!(y::MIVector{T}, A::MIOperator{T}, x::MIVector{T}) wh
     check(ccall((:expv_mi_op_apply, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint), A.h, x.ptr, DEVICE, y.ptr, DEVICE), ctx().h)
     y
 end
+# a REAL operator on complex vectors (expv_mi_op_apply_complex): the operator is read as it is stored, no promoted copy
+const MIReal = Union{Float64, Float32}
+function LinearAlgebra.mul!(y::MIVector{Complex{R}}, A::MIOperator{R}, x::MIVector{Complex{R}}) where {R <: MIReal}
+    check(ccall((:expv_mi_op_apply_complex, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint), A.h, x.ptr, DEVICE, y.ptr, DEVICE), ctx().h)
+    y
+end
 
 # ---- KrylovSubspace on the device ----------------------------------------------------------------------------------
 # Ks.V is an MIMatrix over library-owned HBM; Ks.H stays a host Matrix{U} (arnoldi.jl:69) that WRAPS the library's host
@@ -703,6 +709,28 @@ function arnoldi(A::MIOperator{T}, b::MIVector{T}; m = min(30, size(A, 1)),
     Ks = mi_subspace(T, ishermitian ? real(T) : T, length(b), m)
     arnoldi!(Ks, A, b; m = m, ishermitian = ishermitian, kw...)
 end
+# Mixed calls -- T = promote_type(eltype(A), eltype(b)) with a real A and a complex b (include/expv_mi.h: expv_mi_arnoldi): the same
+# entries with the subspace and b of the operator's complex type; a real symmetric A runs lanczos! with U = R.  New dispatch only.
+function arnoldi!(Ks::MIKs{Complex{R}, U}, A::MIOperator{R}, b::MIVector{Complex{R}};
+                  tol::Real = 1.0e-7, m::Int = min(Ks.maxiter, size(A, 1)), ishermitian::Bool = LinearAlgebra.ishermitian(A),
+                  opnorm = nothing, iop::Int = 0, init::Int = 0, kw...) where {R <: MIReal, U}
+    grow = m > Ks.maxiter
+    check(ccall((:expv_mi_arnoldi, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{ArnoldiOpts}),
+                handle(Ks), A.h, b.ptr, DEVICE, opts(m, tol, iop, init, ishermitian; flags = DEFER_TAIL)), ctx().h)
+    grow && ((Ks.V, Ks.H) = views_of(Complex{R}, U, handle(Ks), size(Ks.V, 1)); Ks.maxiter = m)
+    sync_fields!(Ks)
+end
+function lanczos!(Ks::MIKs{Complex{R}, U}, A::MIOperator{R}, b::MIVector{Complex{R}};
+                  tol::Real = 1.0e-7, m::Int = min(Ks.maxiter, size(A, 1)), opnorm = nothing, init::Int = 0, kw...) where {R <: MIReal, U}
+    check(ccall((:expv_mi_lanczos, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{ArnoldiOpts}),
+                handle(Ks), A.h, b.ptr, DEVICE, opts(m, tol, 0, init, 1; flags = DEFER_TAIL)), ctx().h)
+    sync_fields!(Ks)
+end
+function arnoldi(A::MIOperator{R}, b::MIVector{Complex{R}}; m = min(30, size(A, 1)),
+                 ishermitian = LinearAlgebra.ishermitian(A), kw...) where {R <: MIReal}
+    Ks = mi_subspace(Complex{R}, ishermitian ? R : Complex{R}, length(b), m)
+    arnoldi!(Ks, A, b; m = m, ishermitian = ishermitian, kw...)
+end
 
 # expv!(w, t, Ks; cache, expmethod)                                                           (src/krylov_phiv.jl:200-280)
 # (the m x m exponential runs on the host inside the library: north_star; `cache` / `expmethod` are accepted and unused)
@@ -725,6 +753,17 @@ function ExponentialUtilities._expv_hb(t::Tt, A::MIOperator{T}, b::MIVector{T}; 
     check(ccall((:expv_mi_expv, lib), Cint,
                 (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Ref{ArnoldiOpts}, Ref{ExpvStats}),
                 ctx().h, A.h, real(t), imag(t), b.ptr, DEVICE, w.ptr, DEVICE, dtype(eltype(w)), opts(m, tol, iop, 0, ishermitian), st), ctx().h)
+    w
+end
+# expv(t, A, b) for a real A and a complex b (expv_mi_expv_realop): exp(-im * t * H) * psi with the real H as it is stored
+function ExponentialUtilities._expv_hb(t::Tt, A::MIOperator{R}, b::MIVector{Complex{R}}; expmethod = nothing, cache = nothing,
+                                       m = min(30, size(A, 1)), tol = 1.0e-7, iop = 0,
+                                       ishermitian = LinearAlgebra.ishermitian(A), opnorm = nothing) where {Tt, R <: MIReal}
+    w = similar(b, Complex{R}, (length(b),))
+    st = Ref(ExpvStats(0, 0, 0, 0, 0.0))
+    check(ccall((:expv_mi_expv_realop, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ref{ArnoldiOpts}, Ref{ExpvStats}),
+                ctx().h, A.h, real(t), imag(t), b.ptr, DEVICE, w.ptr, DEVICE, opts(m, tol, iop, 0, ishermitian), st), ctx().h)
     w
 end
 # expv(t, A, b; mode = :error_estimate, ...)                                                  (src/krylov_phiv.jl:145-160)
@@ -943,6 +982,40 @@ phiv_timestep(t::Real, A::MIOperator{T}, B::MIVecOrMat{T}; kwargs...) where {T} 
     phiv_timestep!(MIArray{T}(undef, size(A, 1)), [Float64(t)], A, B; kwargs...)
 expv_timestep(ts::Vector{<:Real}, A::MIOperator{T}, b::MIVector{T}; kwargs...) where {T} = phiv_timestep(ts, A, b; kwargs...)
 expv_timestep(t::Real, A::MIOperator{T}, b::MIVector{T}; kwargs...) where {T} = phiv_timestep(t, A, b; kwargs...)
+# phiv_timestep! / expv_timestep! for a real A with complex B, U and caches (expv_mi_phiv_timestep_realop)
+function phiv_timestep!(U::MIVecOrMat{Complex{R}}, ts::AbstractVector{tType}, A::MIOperator{R}, B::MIVecOrMat{Complex{R}};
+                        tau::Real = 0.0, m::Int = min(10, size(A, 1)), tol::Real = 1.0e-7, opnorm = nothing, iop::Int = 0,
+                        correct::Bool = false, caches = nothing, adaptive = false, delta::Real = 1.2,
+                        ishermitian::Bool = LinearAlgebra.ishermitian(A), gamma::Real = 0.8, NA::Int = 0,
+                        verbose = false) where {R <: MIReal, tType <: Real}
+    length(ts) == ncols(U) || throw(AssertionError("Dimension mismatch"))
+    (size(U, 1) == size(A, 1) == size(B, 1)) || throw(AssertionError("Dimension mismatch"))
+    tsv = ts isa Vector{Float64} ? ts : Vector{Float64}(ts)
+    has_opn, opn = 0, 0.0
+    if opnorm !== nothing
+        has_opn, opn = 1, Float64(opnorm isa Number ? opnorm : opnorm(A, Inf))
+    end
+    o = Ref(TimestepOpts(tau, tol, delta, gamma, opn, has_opn, m, iop, correct, adaptive, ishermitian, verbose, 0, 0, 0, NA,
+                         verbose ? println_ptr() : warn_ptr(), C_NULL))
+    st = Ref(TimestepStats(0, 0, 0, 0, 0, 0))
+    check(ccall((:expv_mi_phiv_timestep_realop, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cvoid}, Int64, Cint,
+                 Ref{TimestepOpts}, Ptr{Cvoid}, Ref{TimestepStats}),
+                ctx().h, A.h, length(tsv), tsv, B.ptr, ld(B), ncols(B), DEVICE, U.ptr, ld(U), DEVICE, o,
+                caches === nothing ? C_NULL : caches.h, st), ctx().h)
+    tsv === ts || copyto!(ts, tsv)
+    U
+end
+function phiv_timestep!(u::MIVector{Complex{R}}, t::Real, A::MIOperator{R}, B::MIMatrix{Complex{R}}; caches = nothing, kwargs...) where {R <: MIReal}
+    phiv_timestep!(u, _singleton_ts(caches, t), A, B; caches = caches, kwargs...)
+    u
+end
+function expv_timestep!(u::MIVector{Complex{R}}, t::Real, A::MIOperator{R}, b::MIVector{Complex{R}}; caches = nothing, kwargs...) where {R <: MIReal}
+    phiv_timestep!(u, _singleton_ts(caches, t), A, b; caches = caches, kwargs...)
+    u
+end
+expv_timestep!(U::MIMatrix{Complex{R}}, ts::AbstractVector{<:Real}, A::MIOperator{R}, b::MIVector{Complex{R}}; kwargs...) where {R <: MIReal} =
+    phiv_timestep!(U, ts, A, b; kwargs...)
 
 # ---- kiops(tau_out, A, u; ...)                                                                      (src/kiops.jl:57-281) ----
 # Returns (w, stats) like the reference: w is n x size(tau_out, 2) (= n x 1: the only reachable case, see DESIGN.md),
